@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- macroblocks/s (encode+decode) on synthetic YUV 4:2:0, MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload gop1080p|config5] [--streams S]
+    python bench.py --gpus N --steps K --warmup W [--workload gop1080p|config5] [--streams S] [--full] [--dump-outputs DIR]
 
 Workloads (BASELINE.json `configs`):
   gop1080p (default; the configuration the metric is quoted on): one step = one GOP-15 (1 i-frame + 14 p-frames,
@@ -26,10 +26,19 @@ rendezvous sockets (RCCL refuses two ranks on one device); the JSON says so (`rc
 The JSON line also carries
   roofline     -- dominant kernel (k_enc_pframe): algorithmic bytes per launch (1284 B per macroblock, SURVEY.md
                   section 8d) / its average HIP-event duration on the context's own stream, against the 8 TB/s HBM peak;
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line):
+  roofline.valu / roofline.issue -- measured in this run by three child runs under rocprofv3 --pmc (live PMC);
+  encode_to_payload -- the encoder with its device entropy stage, timed beside the headline;
   cpu_baseline -- the CPU oracle (a port of the reference's algorithm with its fork/join structure; the Rust reference
                   itself cannot be built here) timed on this node's host cores on GOPs of one stream of the workload;
   extra        -- (N = 1) single-stream figures (S = 1, S = 8; per-frame launches vs one HIP graph per GOP) and BASELINE
                   config #4 (4K x 300 frames) at kernel / +PCIe / end-to-end scope.
+--full also checks the decoder's framebuffer against the encoder's reconstruction after the timed steps.
+
+--dump-outputs DIR writes what the timed path computed in its last step (the decoded frames, the coefficients, motion vectors and
+coded-macroblock flags of the last frame operation) as DIR/<name>.npy in float32; an output larger than its share of the 60 MB
+budget is a fixed, seeded sample of runs of consecutive elements.  The inputs are generated from fixed seeds, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -87,6 +96,12 @@ def parse():
                     help="skip the decoder == encoder check (ablation builds of the kernels produce invalid results by construction)")
     ap.add_argument("--no-two-stream", action="store_true",
                     help="skip the two-stream variant of the entropy measurement (profiling runs: keeps per-kernel durations free of time-slicing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the decoder == encoder check, the entropy-stage measurement, the live "
+                         "PMC passes, the extra configurations and the CPU baseline (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (decoded frames, coefficients, motion vectors, coded "
+                         "flags; float32, a fixed seeded sample of the larger ones) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -401,6 +416,13 @@ class StreamSet:
         self.dec.check()
         assert np.array_equal(self.enc.prev_frame(), self.dec.framebuffer()), "decoder framebuffer != encoder reconstruction"
 
+    def outputs(self):
+        """what the last step handed over, as (name, device pointer, elements, dtype): the decoded last frame of every stream (fused
+        crop) and the encoder's outputs of the last frame operation"""
+        S, n_mb = self.S, self.n_mb
+        return [("decoded_frames", self.out_frames, S * self.fb, np.uint8), ("coefficients", self.coef, S * n_mb * 256, np.int16),
+                ("motion_vectors", self.mv, S * n_mb * 2, np.int8), ("coded_macroblocks", self.has, S * n_mb, np.uint8)]
+
     def coded_fraction(self):
         h = np.empty(self.S * self.n_mb, np.uint8)
         self.ctx.download(h, self.has)
@@ -599,6 +621,13 @@ class GopBatchSet:
         want = np.concatenate([pf.plane_y.image()[:H, :W].reshape(-1), pf.plane_u.image()[:H // 2, :W // 2].reshape(-1),
                                pf.plane_v.image()[:H // 2, :W // 2].reshape(-1)])
         assert np.array_equal(last, want), "display-order output frame != crop of the framebuffer"
+
+    def outputs(self):
+        """what the last step handed over, as (name, device pointer, elements, dtype): every decoded frame of the stream in display order and
+        the encoder's outputs of the last frame operation (the slots of its window)"""
+        n, n_mb = self.active(min(self.gop, self.n_frames) - 1), self.n_mb
+        return [("decoded_frames", self.out_frames, self.S * self.n_frames * self.fb, np.uint8), ("coefficients", self.coef, n * n_mb * 256, np.int16),
+                ("motion_vectors", self.mv, n * n_mb * 2, np.int8), ("coded_macroblocks", self.has, n * n_mb, np.uint8)]
 
     def coded_fraction(self):
         h = np.empty(self.slots * self.n_mb, np.uint8)
@@ -1270,6 +1299,36 @@ def live_pmc(args, S, W, H, Q, NF, per_pass_timeout=60):
     return res
 
 
+DUMP_ELEMENTS = {"decoded_frames": 8 << 20, "coefficients": 4 << 20, "motion_vectors": 2 << 20, "coded_macroblocks": 1 << 20}   # float32: 60 MB in all
+DUMP_RUN = 16384          # elements per sampled run of a larger output
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ss, out_dir):
+    """--dump-outputs: the outputs of the last timed step (ss.outputs()) as out_dir/<name>.npy, float32 (every value is an 8- or 16-bit
+    integer: exact).  An output above its DUMP_ELEMENTS share is sampled: runs of DUMP_RUN consecutive elements at offsets drawn with
+    DUMP_SEED, in ascending order -- the same positions on every run with the same arguments.  Returns {name: what was written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    ss.sync()
+    written = {}
+    for name, ptr, n, dtype in ss.outputs():
+        limit = DUMP_ELEMENTS[name]
+        if n <= limit:
+            a = np.empty(n, dtype)
+            ss.ctx.download(a, ptr)
+            how = "whole"
+        else:
+            runs = np.sort(np.random.default_rng(DUMP_SEED).choice(n // DUMP_RUN, limit // DUMP_RUN, replace=False))
+            a = np.empty((len(runs), DUMP_RUN), dtype)
+            for i, r in enumerate(runs):                  # r * DUMP_RUN + DUMP_RUN <= n: every run lies inside the buffer
+                ss.ctx.download(a[i], ptr + int(r) * DUMP_RUN * a.itemsize)
+            a = a.reshape(-1)
+            how = f"{len(runs)} seeded runs of {DUMP_RUN} of {n} elements"
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+        written[name] = {"elements": int(a.size), "of": int(n), "source_dtype": np.dtype(dtype).name, "sample": how}
+    return written
+
+
 # ---------------------------------------------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -1416,15 +1475,22 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     sections["timed"] = el
-    if not args.no_verify:
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        t1 = time.perf_counter()
+        dumped = dump_outputs(ss, args.dump_outputs)  # before anything else runs on the sessions' buffers
+        sections["dump_outputs"] = time.perf_counter() - t1
+    if args.full and not args.no_verify:
         ss.verify()                                   # decoder output == encoder reconstruction, no bad motion vector
     coded_frac = ss.coded_fraction()
     kern_ms = {k: float(np.mean([timer.ms(a, b) for a, b in v])) for k, v in ev.items() if v}
     pe_ms = kern_ms.get("k_enc_pframe", float("nan"))
 
-    t1 = time.perf_counter()
-    ent = None if args.no_entropy else entropy_side(ss, timer, args)
-    sections["entropy"] = time.perf_counter() - t1
+    ent = None
+    if args.full and not args.no_entropy:
+        t1 = time.perf_counter()
+        ent = entropy_side(ss, timer, args)
+        sections["entropy"] = time.perf_counter() - t1
 
     total_mb, el_max = float(args.steps) * NF * S * n_mb, el
     per_rank = None
@@ -1448,14 +1514,14 @@ def main():
         achieved = launch_mbs * BYTES_PER_MB_PENC / (pe_ms * 1e-3) / 1e9
         traffic, n_valu, traffic_source, traffic_waves = traffic_from_profiles(S, W, H, Q)
         live = None
-        t1 = time.perf_counter()
-        if world == 1 and not EMU and not args.no_live_pmc:
+        if world == 1 and not EMU and args.full and not args.no_live_pmc:
+            t1 = time.perf_counter()
             live = live_pmc(args, S, W, H, Q, NF)     # child processes on the same GPU (288 GB: room for their copy of the workload)
             if live:
                 traffic, n_valu, traffic_waves = live["traffic_bytes"], live["valu_wave_instructions"], live["wavefronts"]
                 traffic_source = ("measured in this run: three child runs of this workload under rocprofv3 --kernel-trace --pmc (FETCH_SIZE x 2 KiB + WRITE_SIZE KiB; "
                                   "SQ_INSTS_VALU, SQ_WAVES), means over the k_enc_pframe launches")
-        sections["live_pmc"] = time.perf_counter() - t1
+            sections["live_pmc"] = time.perf_counter() - t1
         valu = issue = None
         if n_valu:
             valu = {"wave_instructions_per_launch": n_valu, "simd_cycles_per_instruction": pe_ms * 1e-3 * GPU_CLOCK_HZ * N_SIMDS / n_valu,
@@ -1484,6 +1550,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": el_max / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1496,7 +1563,7 @@ def main():
                        "world": world, "visible_gpus": None if EMU else int(pkg._lib.load().pfv_device_count()),
                        "same_code_path_for_every_n": "one main() for N = 1 and for a rank of N > 1 (torch-free process; StreamSet.step in the timed loop); at N > 1 the "
                                                      "table broadcast, the barriers and the counter reduction go through comm.py, at N = 1 they are no-ops; the "
-                                                     "extra / cpu_baseline / live-PMC legs run on rank 0 at N = 1 only, after the timed region"},
+                                                     "extra / cpu_baseline / live-PMC legs (--full) run on rank 0 at N = 1 only, after the timed region"},
             "control_plane": {"backend": comm.backend if comm is not None else None, "shared_gpu": bool(share and world > 1), "emulated": EMU,
                               "rccl_error": comm.rccl_error if comm is not None else None, "ranks": per_rank,
                               "collectives": "assignment-table broadcast + barriers + counter all-reduce only (no data-path collective); "
@@ -1548,8 +1615,10 @@ def main():
                                "fuse (src/dec.rs:195-197, 209-211); frac_of_hbm_peak_survey_bytes counts SURVEY 8d's figure alone (768 / 1 028 B for the decoders)")
         if ent:
             res["encode_to_payload"] = ent
-        host_gop = ss.host_frames(0, min(GOP, NF)) if (world == 1 and not args.no_cpu_baseline) else None
-        if world == 1 and not args.no_extra and not EMU:
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "dtype": "float32", "arrays": dumped}
+        host_gop = ss.host_frames(0, min(GOP, NF)) if (world == 1 and args.full and not args.no_cpu_baseline) else None
+        if world == 1 and args.full and not args.no_extra and not EMU:
             extra = {}
             if args.workload == "config5":
                 t1 = time.perf_counter()
@@ -1576,13 +1645,13 @@ def main():
                     extra[name] = fn()
                     sections["extra." + name] = time.perf_counter() - t1
             res["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             t1 = time.perf_counter()
             res["cpu_baseline"] = cpu_baseline(W, H, Q, host_gop, n_mb, budget_s=4.0 if EMU else 24.0)
             sections["cpu_baseline"] = time.perf_counter() - t1
             if res["cpu_baseline"].get("pframe_encode_value"):
                 res["pframe_encode"]["vs_cpu_baseline"] = res["pframe_encode"]["value"] / res["cpu_baseline"]["pframe_encode_value"]
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = None                # rank 0 at N = 1 only
         sections["total"] = time.perf_counter() - t_start
         res["sections_s"] = {k: round(v, 3) for k, v in sections.items()}

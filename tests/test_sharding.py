@@ -305,7 +305,7 @@ def test_bench_self_launch_two_ranks():
     the control plane (table broadcast, barriers, counter reduction) runs on the TCP rendezvous of comm.py (RCCL needs a GPU per
     rank), rank 0 prints the line."""
     res = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--streams", "2", "--width", "64", "--height", "48", "--frames", "3",
-                      "--no-entropy"])
+                      "--no-entropy", "--full"])
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["control_plane"]["backend"] == "tcp"
     assert res["rccl_ranks"] == 0 and res["control_plane"]["emulated"] is True
     # whole-job count: 2 ranks x 2 streams x 3 frames x 20 macroblocks per step
@@ -320,7 +320,7 @@ def test_bench_self_launch_two_ranks():
 def test_bench_config5_single_rank_fields():
     """config-5 workload (one stream per GPU, seed = base + rank) and the cpu_baseline fields, at a toy geometry"""
     res = _run_bench(["--workload", "config5", "--steps", "1", "--warmup", "0", "--width", "64", "--height", "48", "--frames", "19",
-                      "--no-entropy"])
+                      "--no-entropy", "--full"])
     assert res["n_gpus"] == 1 and res["config"]["workload"].startswith("config5") and res["config"]["streams_per_gpu"] == 1
     # GOP-batched by default: the 15 + 4 frames are two GOPs = two slots per launch; the whole-job count still is frames x macroblocks
     assert res["config"]["gop_batched"] is True and res["config"]["slots_per_launch"] == 2
@@ -338,6 +338,84 @@ def test_bench_config5_single_rank_fields():
     assert len(cb["passes_of_the_winner"]) == 3 and cb["passes_of_the_winner"][0] <= cb["value"] <= cb["passes_of_the_winner"][2] + 1
     assert cb["value_best"] >= 0.6 * cb["value_1thread"]
     assert set(res["sections_s"]) >= {"setup", "timed", "cpu_baseline"} and res["step_roofline"]["algorithmic_bytes_per_macroblock"] > 2000
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, pkg, oracle):
+    """a plain run (no --full) sets up, warms up, times --steps steps and prints the headline line -- no check, side measurement or CPU
+    baseline beside it; --dump-outputs writes what the last timed step computed: the same arrays on every run with the same arguments,
+    and the oracle's values for the same streams (bench.py's seed table)"""
+    import importlib
+    W, H, S, NF, Q = 64, 48, 2, 3, 5
+    args = ["--steps", "2", "--warmup", "1", "--streams", str(S), "--width", str(W), "--height", str(H), "--frames", str(NF), "--quality", str(Q)]
+    runs = [_run_bench([*args, "--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for res in runs:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(res) and res["full"] is False
+        assert res["steps"] == 2 and abs(res["value"] * res["ms_per_step"] * 1e-3 - NF * S * 20) < 1e-6
+        assert not {"cpu_baseline", "extra", "encode_to_payload"} & set(res)
+        assert set(res["sections_s"]) == {"setup", "timed", "dump_outputs", "total"}
+    names = ("decoded_frames", "coefficients", "motion_vectors", "coded_macroblocks")
+    assert set(runs[0]["dumped_outputs"]["arrays"]) == set(names)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    for n in names:
+        assert got[n].dtype == np.float32 and np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+    shard = importlib.import_module("pretty_fast_video_amd.shard")
+    want = {n: [] for n in names}
+    for seed in shard.assign_streams(S, 1, pkg.synth.SEED)[:, 1]:
+        src = pkg.SyntheticStream(W, H, seed=int(seed))
+        enc = oracle.encoder(W, H, Q)
+        enc.encode_iframe(src.frame(0))
+        for t in range(1, NF):
+            mv, has, coef = enc.encode_pframe(src.frame(t))
+        pf = pkg.VideoFrame.from_packed(W, H, enc.prev_frame(), padded=True)       # decoder output == encoder reconstruction, cropped
+        want["decoded_frames"].append(np.concatenate([pf.plane_y.image()[:H, :W].reshape(-1), pf.plane_u.image()[:H // 2, :W // 2].reshape(-1),
+                                                      pf.plane_v.image()[:H // 2, :W // 2].reshape(-1)]))
+        want["coefficients"].append(coef.reshape(-1))
+        want["motion_vectors"].append(mv.reshape(-1))
+        want["coded_macroblocks"].append(has.reshape(-1))
+    for n in names:
+        assert np.array_equal(got[n], np.concatenate(want[n]).astype(np.float32)), n
+
+
+def test_bench_dump_samples_large_outputs_at_fixed_positions(tmp_path, monkeypatch):
+    """an output above its share of the dump budget is written as seeded runs of consecutive elements, in ascending order, at the same
+    positions every time; the shares add up to at most 64 MB of float32"""
+    import bench
+    assert sum(bench.DUMP_ELEMENTS.values()) * 4 <= 64 << 20
+    monkeypatch.setitem(bench.DUMP_ELEMENTS, "coefficients", 64)
+    monkeypatch.setattr(bench, "DUMP_RUN", 8)
+    bufs = {"decoded_frames": np.arange(100, dtype=np.uint8), "coefficients": np.arange(1003, dtype=np.int16),
+            "motion_vectors": np.arange(-50, 50, dtype=np.int8), "coded_macroblocks": np.ones(40, np.uint8)}
+    base, offs = 4096, {}
+    mem = np.zeros(base + sum(b.nbytes for b in bufs.values()), np.uint8)
+    for n, b in bufs.items():
+        offs[n] = base
+        mem[base:base + b.nbytes] = b.view(np.uint8)
+        base += b.nbytes
+
+    class Ctx:
+        def download(self, dst, src):
+            d = dst.view(np.uint8)
+            assert offs["decoded_frames"] <= src and src + d.size <= len(mem)
+            d[:] = mem[src:src + d.size]
+
+    class Set:
+        ctx = Ctx()
+
+        def sync(self):
+            pass
+
+        def outputs(self):
+            return [(n, offs[n], b.size, b.dtype) for n, b in bufs.items()]
+
+    w1, w2 = bench.dump_outputs(Set(), str(tmp_path / "1")), bench.dump_outputs(Set(), str(tmp_path / "2"))
+    assert w1 == w2 and w1["coefficients"]["elements"] == 64 and w1["decoded_frames"]["sample"] == "whole"
+    for n, b in bufs.items():
+        a = np.load(tmp_path / "1" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "2" / f"{n}.npy"))
+        if n != "coefficients":
+            assert np.array_equal(a, b.astype(np.float32))
+    runs = np.load(tmp_path / "1" / "coefficients.npy").astype(np.int64).reshape(8, 8)
+    assert np.all(runs[:, 0] % 8 == 0) and np.all(np.diff(runs, axis=1) == 1) and np.all(np.diff(runs[:, 0]) > 0) and runs[-1, -1] < 1003
 
 
 @pytest.mark.parametrize("mode", ["self", "env", "torchrun"])

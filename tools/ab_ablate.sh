@@ -10,6 +10,6 @@ done
 for rep in 1 2; do
   for v in $names; do
     if [ $v = full ]; then unset PFV_HIP_LIB; else export PFV_HIP_LIB=/tmp/lib_$v.so; fi
-    python bench.py --no-cpu-baseline --no-entropy --no-verify --steps 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['kernels']['k_enc_pframe']['avg_launch_ms']*1000,1))"
+    python bench.py --full --no-cpu-baseline --no-entropy --no-verify --steps 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['kernels']['k_enc_pframe']['avg_launch_ms']*1000,1))"
   done
 done

@@ -14,7 +14,7 @@ for spec in "$@"; do
 done
 for r in $(seq 1 $ROUNDS); do
   for name in "${names[@]}"; do
-    PFV_HIP_LIB=/tmp/libpfv_$name.so timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-entropy --no-live-pmc $BENCH_ARGS > $OUT/$name.$r.json 2>$OUT/$name.$r.err || { echo "$name round $r failed"; tail -3 $OUT/$name.$r.err; }
+    PFV_HIP_LIB=/tmp/libpfv_$name.so timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-entropy --no-live-pmc $BENCH_ARGS > $OUT/$name.$r.json 2>$OUT/$name.$r.err || { echo "$name round $r failed"; tail -3 $OUT/$name.$r.err; }
   done
 done
 python - "$OUT" "$ROUNDS" "${names[@]}" <<'PY'

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; exit 1; }
 echo "== pytest"; timeout 1200 python -m pytest tests -m gpu -x -q -k "sparse_coded or low_motion or synth or pframe_plane or golden or session_small or benched" 2>&1 | tail -8 | tee $OUT/pytest_gpu.log
-echo "== bench"; timeout 900 python bench.py --no-cpu-baseline --no-two-stream --no-entropy 2>$OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err
+echo "== bench"; timeout 900 python bench.py --full --no-cpu-baseline --no-two-stream --no-entropy 2>$OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err
 python - <<PY
 import json
 r = json.load(open("$OUT/bench.json"))

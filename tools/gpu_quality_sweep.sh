@@ -5,7 +5,7 @@ TAG=${1:-qsweep}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1
 for q in ${@:-0 2 5 8 10}; do
-  timeout 600 python bench.py --quality $q --steps 6 --warmup 2 --no-extra --no-cpu-baseline --no-two-stream 2>$OUT/q$q.err > $OUT/q$q.json || { echo "q$q failed"; tail -3 $OUT/q$q.err; continue; }
+  timeout 600 python bench.py --full --quality $q --steps 6 --warmup 2 --no-extra --no-cpu-baseline --no-two-stream 2>$OUT/q$q.err > $OUT/q$q.json || { echo "q$q failed"; tail -3 $OUT/q$q.err; continue; }
   python - $q $OUT/q$q.json <<'PY'
 import json, sys
 q, f = sys.argv[1:3]

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; exit 1; }
 echo "== pytest -m gpu -k '$KEXPR'"; timeout 1200 python -m pytest tests -m gpu -x -q -k "$KEXPR" 2>&1 | tail -12 | tee $OUT/pytest_gpu.log
-echo "== bench"; timeout 600 python bench.py --no-extra --no-cpu-baseline --no-two-stream 2>$OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err
+echo "== bench"; timeout 600 python bench.py --full --no-extra --no-cpu-baseline --no-two-stream 2>$OUT/bench.err > $OUT/bench.json; tail -3 $OUT/bench.err
 python - <<PY
 import json
 r = json.load(open("$OUT/bench.json"))

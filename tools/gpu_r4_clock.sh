@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $OUT/counters_avail.txt 2>&1; grep -c "" $OUT/counters_avail.txt; grep -o "SQ_[A-Z_0-9]*\|GRBM_[A-Z_0-9]*\|SQC_[A-Z_0-9]*" $OUT/counters_avail.txt | sort -u | tr '\n' ' ' | head -c 6000; echo
 run() { # name, counters...
   name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" -f csv -d $OUT/$name -o $name -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-two-stream --no-extra --no-entropy --no-live-pmc > $OUT/$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" -f csv -d $OUT/$name -o $name -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-two-stream --no-extra --no-entropy --no-live-pmc > $OUT/$name.log 2>&1
   f=$(find $OUT/$name -name "*counter_collection.csv" | head -1)
   k=$(find $OUT/$name -name "*kernel_trace.csv" | head -1)
   if [ -n "$f" ]; then python $R/tools/pmc_summary.py "$f" > $OUT/$name.summary.txt; grep "k_enc\|k_dec" $OUT/$name.summary.txt; [ -n "$k" ] && cp "$k" $OUT/$name.kernel_trace.csv; cp "$f" $OUT/$name.counters.csv; rm -rf $OUT/$name; else tail -5 $OUT/$name.log; fi

@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 BARGS="--steps 4 --warmup 2 --no-cpu-baseline --no-extra --no-entropy --no-live-pmc"
 prof() {  # name, form
-  ( cd /tmp && export TMPDIR=/tmp && PFV_BENCH_PENC_FORM=$2 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$1 -o p -- python $R/bench.py $BARGS > $OUT/prof_$1.log 2>&1 )
+  ( cd /tmp && export TMPDIR=/tmp && PFV_BENCH_PENC_FORM=$2 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$1 -o p -- python $R/bench.py --full $BARGS > $OUT/prof_$1.log 2>&1 )
   local f=$(find $OUT/prof_$1 -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/stats_$1.csv
   rm -rf $OUT/prof_$1
@@ -32,7 +32,7 @@ PY
 echo "== bench, HIP events around the encode call (both kernels), interleaved"
 for r in $(seq 1 $ROUNDS); do
   for form in 1 2; do
-    PFV_BENCH_PENC_FORM=$form timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-entropy --no-live-pmc > $OUT/ab_form$form.$r.json 2>$OUT/ab_form$form.$r.err
+    PFV_BENCH_PENC_FORM=$form timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-entropy --no-live-pmc > $OUT/ab_form$form.$r.json 2>$OUT/ab_form$form.$r.err
   done
 done
 python - $OUT $ROUNDS <<'PY'

@@ -8,9 +8,9 @@ for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   lib=/tmp/libpfv_$name.so
   bash tools/build_lib.sh $lib $flags 2>$OUT/$name.build.err || { echo "$name: build failed"; tail -3 $OUT/$name.build.err; continue; }
-  PFV_HIP_LIB=$lib timeout 600 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $OUT/$name.json 2>$OUT/$name.err
+  PFV_HIP_LIB=$lib timeout 600 python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $OUT/$name.json 2>$OUT/$name.err
   cd /tmp; export TMPDIR=/tmp
-  PFV_HIP_LIB=$lib timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$name -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-entropy > /dev/null 2>&1
+  PFV_HIP_LIB=$lib timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$name -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-entropy > /dev/null 2>&1
   cd $R
   python - "$name" "$OUT/$name.json" "$OUT/prof_$name/p_kernel_stats.csv" <<'PY'
 import sys, json, csv

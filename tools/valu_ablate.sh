@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $names; do
   if [ $v = full ]; then unset PFV_HIP_LIB; else export PFV_HIP_LIB=/tmp/lib_$v.so; fi
   rm -rf /tmp/pmc_$v
-  timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES -f csv -d /tmp/pmc_$v -o p -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-entropy --no-verify > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES -f csv -d /tmp/pmc_$v -o p -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-entropy --no-verify > /dev/null 2>&1
   f=$(find /tmp/pmc_$v -name "*counter_collection.csv" | head -1)
   python3 - "$v" "$f" <<'PY'
 import csv, sys, collections
