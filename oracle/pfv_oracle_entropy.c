@@ -172,7 +172,9 @@ static void rle_create_huffman(htree *t, const int32_t table[16])
     for (int i = 0; i < 16; i++) if (table[i] > max) max = table[i];
     uint8_t tb[16];
     for (int i = 0; i < 16; i++) {
-        if (table[i] > 0) { int32_t v = (int32_t)(((int64_t)table[i] * 255) / max); tb[i] = (uint8_t)(v < 1 ? 1 : v); }
+        /* x * 255 is an i32 product in a release build: it wraps past 8 421 504 (oracle/ENTROPY_WIDTHS.md); the division
+         * after it is signed and truncates toward zero */
+        if (table[i] > 0) { int32_t v = (int32_t)((uint32_t)table[i] * 255u) / max; tb[i] = (uint8_t)(v < 1 ? 1 : v); }
         else tb[i] = 0;
     }
     huff_from_table(t, tb);
@@ -204,6 +206,21 @@ static int huff_read(const htree *t, bitr *r, uint64_t max_bits)
     }
     r->pos = (uint64_t)((int64_t)r->pos - ((int64_t)read_bits - (int64_t)c.len));
     return c.symbol;
+}
+
+/* rle_create_huffman + assign_codes for `n` 16-bin histograms on their own: the normalised table, code values (first branch in
+ * bit 0) and code lengths of every symbol (length 0 = absent, or the single leaf of a one-symbol tree) */
+PFVO_API void pfvo_huffman_from_histogram(const int32_t *hists, int n, uint8_t *tables, uint32_t *code_val, uint8_t *code_len)
+{
+    for (int i = 0; i < n; i++) {
+        htree t;
+        rle_create_huffman(&t, hists + (size_t)i * 16);
+        for (int k = 0; k < 16; k++) {
+            tables[(size_t)i * 16 + k] = t.table[k];
+            code_val[(size_t)i * 16 + k] = t.codes[k].val;
+            code_len[(size_t)i * 16 + k] = (uint8_t)t.codes[k].len;
+        }
+    }
 }
 
 /* ---------------------------------------------------------------- src/lib.rs:96-158 test_entropy as a callable

@@ -177,6 +177,60 @@ int pfv_selfcheck_float_path(pfv_ctx *ctx, int part, uint64_t arg, uint64_t *che
     return PFV_OK;
 }
 
+// ------------------------------------------------------------------ histogram -> table + codes, host or device builder (csrc/pfv_selfcheck.h)
+int pfv_selfcheck_huffman(pfv_ctx *ctx, const int32_t *hists, int n, int on_device, uint8_t *tables, uint32_t *code_val, uint8_t *code_len)
+{
+    if (n < 0 || (n > 0 && (!hists || !tables || !code_val || !code_len))) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_selfcheck_huffman: bad argument");
+    if (!on_device) {
+        for (int i = 0; i < n; i++) {
+            std::array<int32_t, 16> h;
+            memcpy(h.data(), hists + (size_t)i * 16, sizeof h);
+            const HuffmanTree tree(normalise_histogram(h));
+            for (int k = 0; k < 16; k++) {
+                tables[(size_t)i * 16 + k] = tree.table()[k];
+                code_val[(size_t)i * 16 + k] = tree.code((uint8_t)k).val;
+                code_len[(size_t)i * 16 + k] = (uint8_t)tree.code((uint8_t)k).len;
+            }
+        }
+        return PFV_OK;
+    }
+    if (!ctx) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_selfcheck_huffman: the device builder needs a context");
+    if (n == 0) return PFV_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t rows = (size_t)n * 16;
+    int32_t *d_h = nullptr;
+    uint8_t *d_t = nullptr, *d_l = nullptr;
+    uint32_t *d_v = nullptr;
+    auto cleanup = [&]() {
+        if (d_h) (void)hipFree(d_h);
+        if (d_t) (void)hipFree(d_t);
+        if (d_l) (void)hipFree(d_l);
+        if (d_v) (void)hipFree(d_v);
+    };
+#define CHK_TRY(expr)                                                                   \
+    do {                                                                                \
+        hipError_t e__ = (expr);                                                        \
+        if (e__ != hipSuccess) { cleanup(); return hip_fail(ctx, e__, #expr); }         \
+    } while (0)
+    CHK_TRY(hipMalloc((void **)&d_h, rows * sizeof(int32_t)));
+    CHK_TRY(hipMalloc((void **)&d_t, rows));
+    CHK_TRY(hipMalloc((void **)&d_l, rows));
+    CHK_TRY(hipMalloc((void **)&d_v, rows * sizeof(uint32_t)));
+    CHK_TRY(hipMemcpy(d_h, hists, rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_chk_huffman, dim3((unsigned)n), dim3(64), 0, ctx->stream, (const int32_t *)d_h, d_t, d_v, d_l);
+    {
+        int rc = launch_check(ctx, "pfv_selfcheck_huffman");
+        if (rc) { cleanup(); return rc; }
+    }
+    CHK_TRY(hipStreamSynchronize(ctx->stream));
+    CHK_TRY(hipMemcpy(tables, d_t, rows, hipMemcpyDeviceToHost));
+    CHK_TRY(hipMemcpy(code_len, d_l, rows, hipMemcpyDeviceToHost));
+    CHK_TRY(hipMemcpy(code_val, d_v, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+#undef CHK_TRY
+    cleanup();
+    return PFV_OK;
+}
+
 #include "pfv_gop.hip"    // GOP-batched stream objects (pfv_gop_encoder, pfv_gop_decoder)
 
 #include "pfv_comm.hip"   // multi-GPU control plane on RCCL (pfv_comm_*)

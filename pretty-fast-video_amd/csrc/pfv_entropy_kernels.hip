@@ -376,10 +376,10 @@ __device__ inline void ent_build_codes_wave(const int32_t *hist_in, uint8_t *tab
         const int32_t o = __shfl_xor(mx, m);
         mx = o > mx ? o : mx;
     }
-    uint32_t t = 0;   // rle_create_huffman (rle.rs:49-66)
+    uint32_t t = 0;   // rle_create_huffman (rle.rs:49-66): h * 255 wraps in i32 (release build), signed division, at least 1
     if (h > 0) {
-        t = (uint32_t)(((uint64_t)(uint32_t)h * 255u) / (uint32_t)mx);
-        t = t < 1u ? 1u : t;
+        const int32_t q = (int32_t)((uint32_t)h * 255u) / mx;
+        t = q < 1 ? 1u : (uint32_t)q;
     }
     const bool present = lane < 16 && t != 0;
     const uint64_t pm = __ballot(present);

@@ -235,14 +235,15 @@ class HuffmanTree {
     int root_ = -1;
 };
 
-// rle_create_huffman (rle.rs:49-66): histogram -> u8 table max(1, x*255/max)
+// rle_create_huffman (rle.rs:49-66): histogram -> u8 table max(1, x*255/max), x*255 wrapping in i32 as a release build does
+// (past a bin of 8 421 504; oracle/ENTROPY_WIDTHS.md), then a signed division
 inline std::array<uint8_t, 16> normalise_histogram(const std::array<int32_t, 16> &hist)
 {
     int32_t mx = 0;
     for (int32_t x : hist) mx = std::max(mx, x);
     std::array<uint8_t, 16> t{};
     for (int i = 0; i < 16; i++)
-        if (hist[i] > 0) t[i] = (uint8_t)std::max<int64_t>(1, (int64_t)hist[i] * 255 / mx);
+        if (hist[i] > 0) t[i] = (uint8_t)std::max<int32_t>(1, (int32_t)((uint32_t)hist[i] * 255u) / mx);
     return t;
 }
 

@@ -27,6 +27,12 @@ extern "C" {
 struct pfv_ctx;
 __attribute__((visibility("default"))) int pfv_selfcheck_float_path(struct pfv_ctx *ctx, int part, uint64_t arg, uint64_t *checked,
                                                                     uint64_t *mismatches, int64_t first_bad[4]);
+/* rle_create_huffman + HuffmanTree::from_table + assign_codes (src/rle.rs:49-66, src/huffman.rs:71-119, :204-217) for `n` 16-bin
+ * histograms (host arrays): on_device = 1 runs the device builder of the entropy stage (ent_build_codes_wave, one wavefront per
+ * histogram), on_device = 0 the host serialisers' normalise_histogram + HuffmanTree.  Out: tables[n][16], code_val[n][16] (first
+ * branch in bit 0), code_len[n][16] (0 = absent symbol or the leaf of a one-symbol tree). */
+__attribute__((visibility("default"))) int pfv_selfcheck_huffman(struct pfv_ctx *ctx, const int32_t *hists, int n, int on_device,
+                                                                 uint8_t *tables, uint32_t *code_val, uint8_t *code_len);
 #ifdef __cplusplus
 }
 #endif

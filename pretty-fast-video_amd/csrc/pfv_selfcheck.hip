@@ -311,4 +311,13 @@ __global__ __launch_bounds__(64) void k_chk_worst_inverse(const ChkTab *__restri
     if (n_cmp_out) atomicAdd(n_cmp_out, cmp);
 }
 
+// pfv_selfcheck_huffman, device side: the entropy stage's table + code builder (ent_build_codes_wave, pfv_entropy_kernels.hip) on
+// one histogram per workgroup of one wavefront; results go straight to the output rows of histogram blockIdx.x (grid = n)
+__global__ __launch_bounds__(64) void k_chk_huffman(const int32_t *__restrict__ hists, uint8_t *tables, uint32_t *code_val, uint8_t *code_len)
+{
+    __shared__ int parent[32], branch[32];
+    const size_t row = (size_t)blockIdx.x * 16;
+    ent_build_codes_wave(hists + row, tables + row, code_val + row, code_len + row, parent, branch);
+}
+
 }  // namespace pfv

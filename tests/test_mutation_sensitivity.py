@@ -93,3 +93,72 @@ def test_rules_unobservable_by_theorem(vectors, rule, value, why):
 
 def test_every_rule_is_covered():
     assert {v[0] for v in VISIBLE} | {v[0] for v in INVISIBLE} == set(onp.DEFAULT_RULES)
+
+
+# ---------------------------------------------------------------------------------------------------- the entropy layer
+# Same idea for the entropy / container layer: the numpy restatement (oracle/pfv_oracle_entropy_np.py RULES) with one rule
+# flipped must change at least one committed vector of tests/golden/entropy_vectors.npz (names: `<output>:<histogram>` for the
+# crafted histograms, `pay_<case>_bytes` for the payloads).
+import entropy_recompute as er                       # noqa: E402
+from entropy_recompute import ent                    # noqa: E402
+
+ENTROPY_VISIBLE = [
+    ("sort", "ties_desc", "src/huffman.rs:81 stable sort: equal frequencies keep symbol order", ("code_val:all_16_equal", "code_val:tie_at_0")),
+    ("insert", "le", "src/huffman.rs:61-69 new node before the first strictly smaller entry", ("code_val:all_16_equal", "code_len:all_16_fib")),
+    ("children", "swapped", "src/huffman.rs:84-88 left = last popped", ("code_val:typical_frame",)),
+    ("bit_order", "msb", "src/huffman.rs:30-32 first branch in bit 0 (LSB-first codes)", ("code_val:typical_frame",)),
+    ("filler", "ge15", "src/rle.rs:18, :31 fillers while run > 15", ("pay_runs_bytes",)),
+    ("trailing", "drop", "src/rle.rs:36-38 trailing run emitted", ("pay_all_zero_bytes",)),
+    ("min1", "none", "src/rle.rs:57 .max(1)", ("table:min1_floor",)),
+    ("table_i32", "wide", "src/rle.rs:57 x * 255 wraps in i32 (release build)", ("table:wrap_8421505", "table:wrap_12311503",
+                                                                                      "table:wrap_20000000", "table:wrap_17M_of_20M")),
+    ("signed_field", "sign_mag", "src/enc.rs:312, :463 write_signed is two's complement", ("pay_runs_bytes",)),
+    ("one_symbol", "one_bit", "src/huffman.rs:99-102, :205-208 a one-leaf tree codes its symbol in 0 bits", ("code_len:one_symbol_0",)),
+    ("pair_order", "size_first", "src/enc.rs:306-311 num_zeroes code first, then coeff_size", ("pay_runs_bytes",)),
+    ("pf_header", "coded_first", "src/enc.rs:414-422 has_mvec bit, then has_coef bit", ("pay_pmixed_bytes",)),
+]
+
+ENTROPY_INVISIBLE = [
+    ("u8_cast", "saturate",
+     "src/rle.rs:57: q = (x * 255) / max <= 255 without wrap (x <= max); with wrap max > 8 421 504 bounds |q| <= 255, and .max(1) "
+     "lifts every negative quotient to 1, so `as u8` never truncates"),
+    ("code_shift", "wide",
+     "src/huffman.rs:31: 16 leaves make a tree at most 15 deep, so (bit as u32) << len shifts by at most 14"),
+    ("freq", "wide",
+     "src/huffman.rs:86: every leaf weighs at most 255, so no sum of at most 16 of them comes near 2^32"),
+]
+
+
+@pytest.fixture(scope="module")
+def entropy_vectors():
+    return er.load()
+
+
+def test_unmutated_entropy_restatement_reproduces_every_vector(entropy_vectors):
+    assert ent.RULES == ent.DEFAULT_RULES
+    assert er.diff(entropy_vectors, er.recompute(entropy_vectors)) == []
+
+
+@pytest.mark.parametrize("rule,value,where,must", ENTROPY_VISIBLE, ids=[v[0] for v in ENTROPY_VISIBLE])
+def test_entropy_vectors_notice_a_flipped_rule(entropy_vectors, rule, value, where, must):
+    ent.RULES[rule] = value
+    try:
+        changed = er.diff(entropy_vectors, er.recompute(entropy_vectors))
+    finally:
+        ent.RULES.update(ent.DEFAULT_RULES)
+    assert changed, f"no committed entropy vector notices {rule}={value} ({where})"
+    assert set(must) <= set(changed), f"{rule}={value}: expected {must} to change, got {changed}"
+
+
+@pytest.mark.parametrize("rule,value,why", ENTROPY_INVISIBLE, ids=[v[0] for v in ENTROPY_INVISIBLE])
+def test_entropy_rules_unobservable_by_theorem(entropy_vectors, rule, value, why):
+    ent.RULES[rule] = value
+    try:
+        changed = er.diff(entropy_vectors, er.recompute(entropy_vectors))
+    finally:
+        ent.RULES.update(ent.DEFAULT_RULES)
+    assert changed == [], f"{rule}={value} was expected to be unobservable ({why}) but changed {changed}"
+
+
+def test_every_entropy_rule_is_covered():
+    assert {v[0] for v in ENTROPY_VISIBLE} | {v[0] for v in ENTROPY_INVISIBLE} == set(ent.DEFAULT_RULES)
