@@ -25,8 +25,9 @@
  *       has_coef      uint8_t[n_mb]          (subblocks.is_some(); coefficients of a skipped macroblock are written as zeros)
  *       planes        uint8_t row-major, stride = width (VideoPlane, src/plane.rs:1-5)
  *     Macroblocks are in raster order (src/common.rs:364-369); planes in Y,U,V order.
- *   - Quantiser tables are int32_t[64] in raster order with every entry in [1, 65535] (the file format stores them as u16,
- *     src/enc.rs:201-215).
+ *   - Quantiser tables are int32_t[64] in raster order (the file format stores them as u16, src/enc.rs:201-215).  Entries of
+ *     tables that encode (they divide, src/dct.rs:95) lie in [1, 65535]; entries of tables that only decode (the decode
+ *     operators, the decoder session) lie in [0, 65535] (decode only multiplies, src/dct.rs:75-86).
  *   - A context is not thread-safe; distinct contexts are independent (one HIP stream each), like distinct Encoder / Decoder
  *     instances with their own rayon pools.  There is no CPU fallback: without a gfx950 device pfv_ctx_create returns
  *     PFV_ERR_NO_DEVICE.
@@ -45,7 +46,8 @@ extern "C" {
 
 typedef enum pfv_status {
     PFV_OK = 0,
-    PFV_ERR_BAD_ARG = -1,   /* null pointer, non-positive size, q entry outside [1,65535], quality outside 0..10 */
+    PFV_ERR_BAD_ARG = -1,   /* null pointer, non-positive size, q entry outside [1,65535] (encode) / [0,65535] (decode),
+                               quality outside 0..10 */
     PFV_ERR_HIP = -2,       /* a HIP runtime call failed; see pfv_last_error() */
     PFV_ERR_NOMEM = -3,
     PFV_ERR_BAD_MV = -4,    /* a motion vector points outside the reference plane (src/common.rs:258-259) */
@@ -138,7 +140,12 @@ PFV_API int pfv_enc_prev_frame(pfv_enc_session *s, uint8_t *out_host);
 /* ------------------------------------------------------------------ decoder session (hot-path half of dec::Decoder)
  * Holds `qtables` and the padded `framebuffer` (src/dec.rs:15-28), n_streams-wide.
  * qtables: n_qtables tables of 64 (header order: intra_l, intra_c, inter_l, inter_c;
- * src/enc.rs:199-215). */
+ * src/enc.rs:199-215), n_qtables in 0..65535 like a header's u16 count (src/dec.rs:89-111;
+ * qtables may be NULL when it is 0).  A packet names a table by a u8 (src/dec.rs:244-246):
+ * only the first 256 are kept; a qidx >= n_qtables (every qidx when there is no table) makes
+ * the decode call fail with PFV_ERR_FORMAT, where the reference panics (src/dec.rs:249-251).
+ * The stream decoders (pfv_decoder, pfv_gop_decoder, pfv_batch_decoder) pass a header's
+ * count on unchanged, so they open any header. */
 typedef struct pfv_dec_session pfv_dec_session;
 
 PFV_API int pfv_dec_session_create(pfv_ctx *ctx, int width, int height, const int32_t *qtables, int n_qtables,

@@ -14,7 +14,8 @@ static int make_qtab(pfv_ctx *ctx, const int32_t q[64], QTab *out, bool decode_o
 {
     if (!q) return fail(ctx, PFV_ERR_BAD_ARG, "q-table is null");
     for (int i = 0; i < 64; i++)
-        if (q[i] < (decode_only ? 0 : 1) || q[i] > 65535) return fail(ctx, PFV_ERR_BAD_ARG, "q-table entry outside [1,65535]");
+        if (q[i] < (decode_only ? 0 : 1) || q[i] > 65535)
+            return fail(ctx, PFV_ERR_BAD_ARG, decode_only ? "q-table entry outside [0,65535]" : "q-table entry outside [1,65535]");
     for (int i = 0; i < 64; i++) {
         out->rcp[i] = biased_rcp(q[i]);
         int z = H_INV_ZIGZAG[i];
@@ -205,11 +206,11 @@ static int launch_check(pfv_ctx *ctx, const char *what)
     return PFV_OK;
 }
 
-static int upload_qtabs(pfv_ctx *ctx, const int32_t *const *tables, int n)
+static int upload_qtabs(pfv_ctx *ctx, const int32_t *const *tables, int n, bool decode_only)
 {
     // the previous user of the pinned mirror has finished: plane-level host calls sync before returning
     for (int i = 0; i < n; i++) {
-        int rc = make_qtab(ctx, tables[i], &ctx->qtab_host[i]);
+        int rc = make_qtab(ctx, tables[i], &ctx->qtab_host[i], decode_only);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->qtab_dev, ctx->qtab_host, n * sizeof(QTab), hipMemcpyHostToDevice, ctx->stream));

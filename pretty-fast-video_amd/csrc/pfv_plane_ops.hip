@@ -11,7 +11,7 @@ PFV_API int pfv_encode_plane(pfv_ctx *ctx, const uint8_t *px, int w, int h, cons
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FrameGeom g = plane_geom(w, h, clear);
     const int32_t *tabs[1] = {q};
-    int rc = upload_qtabs(ctx, tabs, 1);
+    int rc = upload_qtabs(ctx, tabs, 1, false);
     if (rc) return rc;
     void *d_src, *d_coef;
     size_t coef_bytes = (size_t)g.mbs_per_frame * 512;
@@ -37,7 +37,7 @@ PFV_API int pfv_encode_plane_delta(pfv_ctx *ctx, const uint8_t *px, int w, int h
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FrameGeom g = plane_geom(w, h, clear);
     const int32_t *tabs[1] = {q};
-    int rc = upload_qtabs(ctx, tabs, 1);
+    int rc = upload_qtabs(ctx, tabs, 1, false);
     if (rc) return rc;
     size_t n = (size_t)g.mbs_per_frame, coef_bytes = n * 512, pad_bytes = (size_t)g.pad_frame_bytes;
     void *d_src, *d_coef, *d_ref, *d_mv, *d_has;
@@ -67,7 +67,7 @@ PFV_API int pfv_decode_plane_into(pfv_ctx *ctx, const int16_t *coef, int bw, int
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FrameGeom g = plane_geom(bw * 16, bh * 16, 0);
     const int32_t *tabs[1] = {q};
-    int rc = upload_qtabs(ctx, tabs, 1);
+    int rc = upload_qtabs(ctx, tabs, 1, true);      // decode only multiplies: 0 is a legal entry (src/dct.rs:75-86)
     if (rc) return rc;
     size_t n = (size_t)bw * bh, coef_bytes = n * 512, pad_bytes = (size_t)g.pad_frame_bytes;
     void *d_coef, *d_out;
@@ -90,7 +90,7 @@ PFV_API int pfv_decode_plane_delta(pfv_ctx *ctx, const int8_t *mv, const uint8_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FrameGeom g = plane_geom(bw * 16, bh * 16, 0);
     const int32_t *tabs[1] = {q};
-    int rc = upload_qtabs(ctx, tabs, 1);
+    int rc = upload_qtabs(ctx, tabs, 1, true);
     if (rc) return rc;
     size_t n = (size_t)bw * bh, coef_bytes = n * 512, pad_bytes = (size_t)g.pad_frame_bytes;
     void *d_coef, *d_ref, *d_mv, *d_has, *d_out;

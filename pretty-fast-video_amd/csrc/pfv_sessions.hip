@@ -579,11 +579,14 @@ PFV_API int pfv_dec_session_create(pfv_ctx *ctx, int width, int height, const in
     *out = nullptr;
     if (width <= 0 || height <= 0 || (width & 1) || (height & 1) || width > 65535 || height > 65535)
         return fail(ctx, PFV_ERR_BAD_ARG, "width/height must be even (src/frame.rs:13) and fit u16");
-    if (!qtables || n_qtables <= 0 || n_qtables > 256 || n_streams <= 0)
+    if ((!qtables && n_qtables > 0) || n_qtables < 0 || n_qtables > 65535 || n_streams <= 0)
         return fail(ctx, PFV_ERR_BAD_ARG, "pfv_dec_session_create: bad q-table set or stream count");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<QTab> tabs((size_t)n_qtables);
-    for (int i = 0; i < n_qtables; i++) {
+    // a header may declare any u16 count of tables (src/dec.rs:89-111), a packet names one by a u8 (:244-246): the first 256 are
+    // all a kernel can read; dec_geom checks every index against the full count.  With no table at all every coded packet fails there.
+    const int n_dev = std::min(n_qtables, 256);
+    std::vector<QTab> tabs((size_t)std::max(n_dev, 1));
+    for (int i = 0; i < n_dev; i++) {
         int rc = make_qtab(ctx, qtables + (size_t)i * 64, &tabs[i], true);
         if (rc) return rc;
     }
