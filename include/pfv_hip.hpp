@@ -88,6 +88,17 @@ struct VideoFrame {
     }
 };
 
+// distortion (pfv_hip_ext.h, "distortion on the device"): 10 log10(255^2 n / sse); +inf for sse == 0, NaN for n == 0
+inline double psnr(uint64_t sse, uint64_t n_samples) { return pfv_psnr(sse, n_samples); }
+// what one Encoder::encode_* call wrote and how far its reconstruction is from the frame it was given (pfv_frame_report)
+struct FrameReport {
+    int type = 0;                    // 1 i-frame, 2 p-frame, 3 drop frame
+    uint32_t packet_bytes = 0;       // 5-byte packet header + payload
+    uint64_t sse[3] = {0, 0, 0};     // Y, U, V; zeros for a drop frame
+    double psnr[3] = {0, 0, 0};
+    double psnr_yuv = 0;
+};
+
 // src/enc.rs:12-188
 class Encoder {
   public:
@@ -134,6 +145,20 @@ class Encoder {
     }
     // packet payloads from the device entropy stage (default) or the host serialisers: same bytes
     void set_device_entropy(bool on) { ctx_.check(pfv_encoder_set_device_entropy(h_, on ? 1 : 0)); }
+    // on: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
+    void set_frame_report(bool on) { ctx_.check(pfv_encoder_set_frame_report(h_, on ? 1 : 0)); }
+    // of the last encode_* call; Error(PFV_ERR_STATE) when reports are off, nothing has been encoded yet or that call failed
+    FrameReport last_report() const
+    {
+        pfv_frame_report r;
+        ctx_.check(pfv_encoder_frame_report(h_, &r));
+        FrameReport out;
+        out.type = (int)r.type;
+        out.packet_bytes = r.packet_bytes;
+        for (int i = 0; i < 3; i++) { out.sse[i] = r.sse[i]; out.psnr[i] = r.psnr[i]; }
+        out.psnr_yuv = r.psnr_yuv;
+        return out;
+    }
 
   private:
     void check_frame(const VideoFrame &f) const   // the asserts of src/enc.rs:76-80

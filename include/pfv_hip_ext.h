@@ -266,6 +266,48 @@ PFV_API int pfv_dec_set_output_strided_dev(pfv_dec_session *s, uint8_t *frames_o
 PFV_API int pfv_dec_session_set_window(pfv_dec_session *s, int first, int count);
 /* 1 (default): packet payloads come from the device entropy stage; 0: from the host serialisers.  Same bytes. */
 PFV_API int pfv_encoder_set_device_entropy(pfv_encoder *e, int on);
+/* ------------------------------------------------------------------ distortion on the device  [B]
+ * How far two frames are apart, measured where they lie: the sum of squared differences per plane and per macroblock, and PSNR from it.
+ * The reference's only rate / quality control is `quality` 0..10 (src/enc.rs:37-51); these say what a setting costs in fidelity without
+ * a frame leaving HBM.  Only pixels inside the picture count (the plane's w x h): padding of a padded operand and the part of an edge
+ * macroblock beyond the picture add nothing.  Integer arithmetic, exact; no atomics and nothing to clear, so a call is two kernel nodes of a
+ * recorded graph.  Each operand is a PACKED frame (pfv_frame_bytes, plane stride = plane width) or a PADDED one (pfv_padded_frame_bytes,
+ * plane stride = pfv_pad16(width): prev_frame / the framebuffer), with its own byte stride between streams; a and b may be the same buffer.
+ *   sse_dev     uint64_t[n_streams][3] (Y, U, V)
+ *   mb_sse_dev  uint32_t[n_streams][pfv_total_blocks], macroblocks in frame order (Y, U, V; raster inside a plane: the index space of mv /
+ *               has_coef), or NULL: the map then goes to scratch of the context / session.  That scratch is allocated by the first call that
+ *               needs it; while the context records a graph such a call returns PFV_ERR_STATE (pass a map buffer, or call once before). */
+enum { PFV_FRAME_PACKED = 0, PFV_FRAME_PADDED = 1 };
+/* stride 0 = frames back to back in the operand's layout.  Asynchronous on the context's stream. */
+PFV_API int pfv_frames_sse_dev(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *a_dev, int a_layout, size_t a_stride,
+                               const uint8_t *b_dev, int b_layout, size_t b_stride, uint64_t *sse_dev, uint32_t *mb_sse_dev);
+/* host buffers, both PACKED; mb_sse_out may be NULL; synchronises */
+PFV_API int pfv_frames_sse(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *a, const uint8_t *b, uint64_t *sse_out,
+                           uint32_t *mb_sse_out);
+/* 10 * log10(255^2 * n_samples / sse) in double; +INFINITY when sse == 0; NaN when n_samples == 0 */
+PFV_API double pfv_psnr(uint64_t sse, uint64_t n_samples);
+/* the frames just handed to pfv_enc_iframe_dev / pfv_enc_pframe_dev against the session's CURRENT prev_frame (= what a decoder will show
+ * for them).  Honours the session's window and frame stride; the outputs keep the full-width [n_streams] layout, entries of slots outside
+ * the window are left alone. */
+PFV_API int pfv_enc_distortion_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint64_t *sse_dev, uint32_t *mb_sse_dev);
+/* packed frames against the decoder session's current framebuffer, same conventions: the session's window, and its output stride
+ * (pfv_dec_set_output_strided_dev; 0 = back to back) as the stride between the frames of consecutive slots */
+PFV_API int pfv_dec_distortion_dev(pfv_dec_session *s, const uint8_t *frames_dev, uint64_t *sse_dev, uint32_t *mb_sse_dev);
+/* pfv_encoder: what the last encode_* call wrote and how far its reconstruction is from the frame it was given.  With reports on, one
+ * more small launch follows the encode kernel and 24 bytes come back with the payload size (or with the host path's downloads); the
+ * stream bytes are the same.  pfv_gop_encoder and pfv_batch_encoder have no reports: their batches are collected late and a batch that
+ * outgrows its arena is encoded again. */
+typedef struct pfv_frame_report {
+    int32_t  type;          /* 1 i-frame, 2 p-frame, 3 drop frame */
+    uint32_t packet_bytes;  /* 5-byte packet header + payload, as written to the stream */
+    uint64_t sse[3];        /* Y,U,V; zeros for a drop frame */
+    double   psnr[3];       /* pfv_psnr per plane */
+    double   psnr_yuv;      /* pfv_psnr(sse[0]+sse[1]+sse[2], all samples of the frame) */
+} pfv_frame_report;
+PFV_API int pfv_encoder_set_frame_report(pfv_encoder *e, int on);               /* default 0 */
+/* of the last encode_* call; PFV_ERR_STATE when reports are off, no frame has been encoded, or that call failed */
+PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out);
+
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);
  * every writer receives exactly the bytes an Encoder of its own would have written.  Per frame step: ONE upload of all

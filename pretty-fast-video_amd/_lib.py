@@ -35,6 +35,7 @@ PFV_OPT_ENTROPY_DECODE = 4
 PFV_OPT_ENTDEC_LANE_BITS, PFV_OPT_ENTDEC_LAUNCHES, PFV_OPT_ENTDEC_INNER_ROUNDS = 5, 6, 7
 PFV_ENTROPY_DECODE_AUTO, PFV_ENTROPY_DECODE_HOST, PFV_ENTROPY_DECODE_DEVICE = 0, 1, 2
 PFV_ENC_TRANSFORM_AUTO, PFV_ENC_TRANSFORM_INT = 0, 1
+PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_frames_sse_dev
 
 
 class PfvError(RuntimeError):
@@ -149,6 +150,13 @@ SIGNATURES = [
     ("pfv_encoder_drain", c_int, [_P, POINTER(_P), POINTER(c_size_t)]),
     ("pfv_encoder_destroy", None, [_P]),
     ("pfv_encoder_set_device_entropy", c_int, [_P, c_int]),
+    ("pfv_frames_sse_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, _P, c_int, c_size_t, _P, _P]),
+    ("pfv_frames_sse", c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    ("pfv_psnr", ctypes.c_double, [ctypes.c_uint64, ctypes.c_uint64]),
+    ("pfv_enc_distortion_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_dec_distortion_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_encoder_set_frame_report", c_int, [_P, c_int]),
+    ("pfv_encoder_frame_report", c_int, [_P, _P]),
     ("pfv_batch_encoder_create", c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(_P)]),
     ("pfv_batch_encoder_frames", _P, [_P]),
     ("pfv_batch_encoder_encode", c_int, [_P, c_int, _P]),

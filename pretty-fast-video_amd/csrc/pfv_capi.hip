@@ -13,6 +13,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #else
 #include "pfv_penc.hip"
 #endif
+#include "pfv_quality_kernels.hip"
 #include "pfv_entropy_kernels.hip"
 #include "pfv_entdec_kernels.hip"
 #include "pfv_synth_kernels.hip"
@@ -66,6 +67,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_launch.hip"
 #include "pfv_plane_ops.hip"
 #include "pfv_sessions.hip"
+#include "pfv_quality.hip"
 #include "pfv_stream_objects.hip"
 #include "pfv_batch_objects.hip"
 #include "pfv_decoder_object.hip"

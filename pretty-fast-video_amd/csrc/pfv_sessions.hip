@@ -98,6 +98,10 @@ struct pfv_enc_session {
     int16_t *st_coef = nullptr;
     int8_t *st_mv = nullptr;
     uint8_t *st_has = nullptr;
+    // distortion (pfv_quality.hip): the macroblock map when the caller passes none, the plane sums and where they land on the host
+    uint32_t *q_map = nullptr;
+    uint64_t *q_sse = nullptr;
+    uint64_t *report_host = nullptr;         // pfv_encoder's frame reports are on: [n_streams][3], page-locked, owned by the encoder
     // device entropy stage (pfv_enc_entropy_enable)
     bool ent_on = false;
     uint32_t ent_cap = 0;
@@ -136,7 +140,9 @@ struct pfv_dec_session {
     uint32_t *st_idx = nullptr;              // sparse coefficient upload (pfv_dec_*_sparse)
     int16_t *st_val = nullptr;
     size_t st_sparse_cap = 0;
+    uint32_t *q_map = nullptr;               // distortion (pfv_quality.hip): the macroblock map when the caller passes none
 };
+static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
 
 extern "C" {
 
@@ -188,7 +194,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -307,6 +313,7 @@ PFV_API int pfv_enc_iframe(pfv_enc_session *s, const uint8_t *frames, int16_t *c
     HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
                                 hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_iframe_dev(s, s->st_frames, s->st_coef))) return rc;
+    if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
@@ -326,6 +333,7 @@ PFV_API int pfv_enc_pframe(pfv_enc_session *s, const uint8_t *frames, int8_t *mv
     HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
                                 hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_pframe_dev(s, s->st_frames, s->st_mv, s->st_has, s->st_coef))) return rc;
+    if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(mv_out, s->st_mv, n * 2, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(has_coef_out, s->st_has, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -620,7 +628,7 @@ PFV_API void pfv_dec_session_destroy(pfv_dec_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val};
+    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;

@@ -55,6 +55,11 @@ struct pfv_encoder {
     PinnedBuf<int8_t> mv;
     PinnedBuf<uint8_t> has;
     PinnedBuf<uint8_t> payload;            // device entropy path: packet payload landing zone
+    // frame reports (pfv_encoder_set_frame_report): the plane sums land in `sums` with the frame's other downloads
+    bool report_on = false;
+    int report_state = 0;                  // 0: no encode_* call yet, 1: `report` describes the last one, -1: the last one failed
+    pfv_frame_report report{};
+    PinnedBuf<uint64_t> sums;              // [3]
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -382,6 +387,22 @@ PFV_API int pfv_encoder_create(pfv_ctx *ctx, int width, int height, int framerat
     return PFV_OK;
 }
 
+// the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
+static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
+{
+    if (!e->report_on) return;
+    pfv_frame_report &r = e->report;
+    const uint64_t ny = (uint64_t)e->width * (uint64_t)e->height, nc = (uint64_t)(e->width / 2) * (uint64_t)(e->height / 2);
+    r.type = type;
+    r.packet_bytes = (uint32_t)packet_bytes;
+    for (int i = 0; i < 3; i++) {
+        r.sse[i] = type == 3 ? 0 : e->sums.data()[i];
+        r.psnr[i] = pfv_psnr(r.sse[i], i ? nc : ny);
+    }
+    r.psnr_yuv = pfv_psnr(r.sse[0] + r.sse[1] + r.sse[2], ny + 2 * nc);
+    e->report_state = 1;
+}
+
 static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
 {
     if (!y || !u || !v) return fail(e->ctx, PFV_ERR_BAD_ARG, "null plane");
@@ -425,6 +446,7 @@ static int encode_on_device(pfv_encoder *e, bool pframe)
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     // from here on prev_frame has moved to this frame: a failure leaves the encoder's reference ahead of the stream
     e->poisoned = true;
+    if (e->report_on && (rc = enc_report_enqueue(s))) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // arrives with the payload size
     rc = pframe ? pfv_enc_pack_pframe_dev(s, s->st_mv, s->st_has, s->st_coef) : pfv_enc_pack_iframe_dev(s, s->st_coef);
     uint32_t nbytes = 0;
     if (!rc) rc = pfv_enc_payload_sizes(s, &nbytes);
@@ -435,6 +457,7 @@ static int encode_on_device(pfv_encoder *e, bool pframe)
     e->out.push_back(pframe ? 2 : 1);
     put_u32(e->out, nbytes);
     e->out.insert(e->out.end(), e->payload.data(), e->payload.data() + nbytes);
+    fill_report(e, pframe ? 2 : 1, 5 + (size_t)nbytes);
     return PFV_OK;
 }
 
@@ -447,10 +470,33 @@ PFV_API int pfv_encoder_set_device_entropy(pfv_encoder *e, int on)
     return PFV_OK;
 }
 
+// Frame reports: with them on, every encode_* call also measures the frame it was given against the reconstruction it leaves in prev_frame
+// (k_sse_mb + k_sse_sum behind the encode kernel) and keeps what it wrote; the stream bytes do not change.
+PFV_API int pfv_encoder_set_frame_report(pfv_encoder *e, int on)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (on && !e->sums.resize(3)) return fail(e->ctx, PFV_ERR_NOMEM, "pinned staging for the frame reports");
+    int rc = enc_report_enable(e->hot, on ? e->sums.data() : nullptr);
+    if (rc) return rc;
+    if (!on || !e->report_on) e->report_state = 0;
+    e->report_on = on != 0;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out)
+{
+    if (!e || !out) return fail(e ? e->ctx : nullptr, PFV_ERR_BAD_ARG, "pfv_encoder_frame_report: bad argument");
+    if (!e->report_on) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_report: reports are off (pfv_encoder_set_frame_report)");
+    if (e->report_state == 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_report: no frame has been encoded yet");
+    if (e->report_state < 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_report: the last encode call failed");
+    *out = e->report;
+    return PFV_OK;
+}
+
 // Encoder::encode_iframe (src/enc.rs:75-123)
 PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;   // until this call has written its packet
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     if (e->device_entropy) return encode_on_device(e, false);      // an i-frame replaces prev_frame entirely: clears a poisoned state
@@ -462,12 +508,14 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
     put_packet(e->out, 1, &payload);
     e->poisoned = false;
+    fill_report(e, 1, 5 + payload.size());
     return PFV_OK;
 }
 // Encoder::encode_pframe (src/enc.rs:125-173)
 PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;   // until this call has written its packet
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     // a previous frame failed after the encoder's reference had advanced but before its packet was written: a p-frame
@@ -482,14 +530,17 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
     put_packet(e->out, 2, &payload);
     e->poisoned = false;
+    fill_report(e, 2, 5 + payload.size());
     return PFV_OK;
 }
 // Encoder::encode_dropframe (src/enc.rs:175-180): an i-frame packet with an empty payload
 PFV_API int pfv_encoder_encode_dropframe(pfv_encoder *e)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:176)");
     put_packet(e->out, 1, nullptr);
+    fill_report(e, 3, 5);
     return PFV_OK;
 }
 // Encoder::finish (src/enc.rs:182-188): EOF packet

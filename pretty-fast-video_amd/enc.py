@@ -15,7 +15,8 @@ from .frame import VideoFrame
 
 
 class Encoder:
-    def __init__(self, writer, width: int, height: int, framerate: int, quality: int, ctx: Context, device_entropy: bool = True):
+    def __init__(self, writer, width: int, height: int, framerate: int, quality: int, ctx: Context, device_entropy: bool = True,
+                 frame_report: bool = False):
         assert 0 <= quality <= 10                                   # src/enc.rs:38
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
@@ -24,6 +25,9 @@ class Encoder:
         self.handle = h
         # packet payloads from the device entropy stage (default) or the host serialisers: same bytes
         ctx.check(ctx._lib.pfv_encoder_set_device_entropy(h, 1 if device_entropy else 0))
+        # frame_report: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
+        if frame_report:
+            ctx.check(ctx._lib.pfv_encoder_set_frame_report(h, 1))
         self.finished = False
         ctx._sessions.add(self)
         self._flush()                                               # header (src/enc.rs:70)
@@ -58,6 +62,15 @@ class Encoder:
         assert not self.finished
         self.ctx.check(self.ctx._lib.pfv_encoder_encode_dropframe(self.handle))
         self._flush()
+
+    @property
+    def last_report(self):
+        """FrameReport of the last encode_* call (pfv_encoder_frame_report); PfvError(PFV_ERR_STATE) when reports are off, nothing has
+        been encoded yet or that call failed"""
+        from .quality import FrameReport, FrameReportStruct
+        r = FrameReportStruct()
+        self.ctx.check(self.ctx._lib.pfv_encoder_frame_report(self.handle, ctypes.byref(r)))
+        return FrameReport(int(r.type), int(r.packet_bytes), tuple(int(v) for v in r.sse), tuple(float(v) for v in r.psnr), float(r.psnr_yuv))
 
     def finish(self):
         assert not self.finished                                    # src/enc.rs:183

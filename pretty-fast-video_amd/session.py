@@ -134,6 +134,21 @@ class EncoderSession(_Geometry):
     def payload_dev(self, stream: int) -> int:
         return int(self.ctx._lib.pfv_enc_payload_dev(self.handle, int(stream)) or 0)
 
+    # distortion: the frames just encoded against the current prev_frame (pfv_enc_distortion_dev) ---------------
+    def distortion_dev(self, frames_dev: int, sse_dev: int, mb_sse_dev: int = 0):
+        """asynchronous on the context's stream; sse_dev uint64 [n_streams][3], mb_sse_dev uint32 [n_streams][total_blocks] or 0 (the
+        map then stays in the session's scratch).  Honours the window and the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_distortion_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sse_dev),
+                                                            ctypes.c_void_p(mb_sse_dev or 0)))
+
+    def distortion(self, frames, mb_map: bool = False, out=None, out_map=None):
+        """squared error per plane, uint64 [n_streams, 3], between `frames` -- the frames handed to the last encode call, as an array
+        (uploaded as it is: with a frame stride set it holds the strided layout) or a device address -- and what a decoder will show for
+        them; with mb_map also the per-macroblock map uint32 [n_streams, total_blocks].  Entries of slots outside the window keep the
+        values of `out` / `out_map` (zeros when not given)."""
+        from .quality import session_distortion
+        return session_distortion(self, self.distortion_dev, frames, mb_map, out, out_map)
+
 
 class DecoderSession(_Geometry):
     def __init__(self, ctx: Context, width: int, height: int, qtables, n_streams: int = 1):
@@ -286,3 +301,14 @@ class DecoderSession(_Geometry):
         out = np.empty((self.n_streams, self.padded_frame_bytes), dtype=np.uint8)
         self.ctx.check(self.ctx._lib.pfv_dec_framebuffer(self.handle, ptr(out)))
         return out
+
+    # distortion: packed frames against the current framebuffer (pfv_dec_distortion_dev) ---------------
+    def distortion_dev(self, frames_dev: int, sse_dev: int, mb_sse_dev: int = 0):
+        self.ctx.check(self.ctx._lib.pfv_dec_distortion_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sse_dev),
+                                                            ctypes.c_void_p(mb_sse_dev or 0)))
+
+    def distortion(self, frames, mb_map: bool = False, out=None, out_map=None):
+        """squared error per plane, uint64 [n_streams, 3], between `frames` (packed originals: an array or a device address) and the
+        decoded frames; see EncoderSession.distortion"""
+        from .quality import session_distortion
+        return session_distortion(self, self.distortion_dev, frames, mb_map, out, out_map)
