@@ -108,6 +108,13 @@ class Encoder {
         ctx_.check(pfv_encoder_create(ctx.handle(), (int)width, (int)height, (int)framerate, quality, &h_));
         flush();   // the header (src/enc.rs:70)
     }
+    // a quality ladder: 1..11 qualities in 0..10, strictly ascending (towards coarser quantisers); the header carries every rung's tables
+    Encoder(std::ostream &writer, size_t width, size_t height, uint32_t framerate, const std::vector<int> &qualities, Context &ctx)
+        : ctx_(ctx), out_(writer), width_(width), height_(height)
+    {
+        ctx_.check(pfv_encoder_create_ladder(ctx.handle(), (int)width, (int)height, (int)framerate, qualities.data(), (int)qualities.size(), &h_));
+        flush();
+    }
     ~Encoder()   // impl Drop (src/enc.rs:28-34): finish if the caller did not
     {
         if (h_) {
@@ -147,6 +154,12 @@ class Encoder {
     void set_device_entropy(bool on) { ctx_.check(pfv_encoder_set_device_entropy(h_, on ? 1 : 0)); }
     // on: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
     void set_frame_report(bool on) { ctx_.check(pfv_encoder_set_frame_report(h_, on ? 1 : 0)); }
+    // quality ladder: the rung of the frames that follow / of the last frame written (before the first frame: the current rung)
+    void set_rung(int rung) { ctx_.check(pfv_encoder_set_rung(h_, rung)); }
+    int rung() const { return pfv_encoder_rung(h_); }
+    int n_rungs() const { return pfv_encoder_rungs(h_); }
+    // byte budget per p-frame payload, 0 = off (pfv_encoder_set_rate)
+    void set_rate(uint32_t pframe_budget) { ctx_.check(pfv_encoder_set_rate(h_, pframe_budget)); }
     // of the last encode_* call; Error(PFV_ERR_STATE) when reports are off, nothing has been encoded yet or that call failed
     FrameReport last_report() const
     {

@@ -308,6 +308,32 @@ PFV_API int pfv_encoder_set_frame_report(pfv_encoder *e, int on);               
 /* of the last encode_* call; PFV_ERR_STATE when reports are off, no frame has been encoded, or that call failed */
 PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out);
 
+/* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
+ * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
+ * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`
+ * holds n_rungs values in 0..10, strictly ascending (1 <= n_rungs <= 11; a higher quality number is a coarser quantiser, src/enc.rs:40-51, so
+ * rung 0 is the finest), rung r owns tables 4r .. 4r + 3 (intra_l, intra_c, inter_l, inter_c) and the px_err of qualities[r].  The rung is a
+ * property of a launch: it applies to every slot of the encode / pack calls that follow pfv_enc_session_set_rung.  A ladder of one rung is
+ * pfv_enc_session_create / pfv_encoder_create, byte for byte.  pfv_batch_encoder and pfv_gop_encoder keep one quality. */
+PFV_API int pfv_enc_session_create_ladder(pfv_ctx *ctx, int width, int height, const int *qualities, int n_rungs, int n_streams,
+                                          pfv_enc_session **out);
+/* A launch recorded in a graph (pfv_graph_begin) keeps the table pointer, min_err and packet indices of the rung at capture time:
+ * pfv_enc_session_set_rung does not reach the replays of an existing graph. */
+PFV_API int pfv_enc_session_set_rung(pfv_enc_session *s, int rung);       /* PFV_ERR_BAD_ARG outside [0, n_rungs) */
+PFV_API int pfv_enc_session_rung(pfv_enc_session *s);                     /* the current rung */
+PFV_API int pfv_enc_session_rungs(pfv_enc_session *s);                    /* n_rungs */
+/* pfv_encoder with a ladder: the header carries 4 * n_rungs tables, rung-major; pfv_encoder_create is the one-rung case. */
+PFV_API int pfv_encoder_create_ladder(pfv_ctx *ctx, int width, int height, int framerate, const int *qualities, int n_rungs, pfv_encoder **out);
+PFV_API int pfv_encoder_set_rung(pfv_encoder *e, int rung);               /* the rung of the frames that follow, on both entropy paths */
+PFV_API int pfv_encoder_rung(pfv_encoder *e);                             /* of the last frame written; before the first frame the current rung */
+PFV_API int pfv_encoder_rungs(pfv_encoder *e);
+/* A p-frame byte budget in payload bytes (the packet adds 5), 0 = off.  One state variable, the current rung (rung 0 is the finest).
+ * A p-frame is encoded at the current rung; with n = its payload bytes: n > pframe_budget moves the rung one step coarser, otherwise
+ * 2 n <= pframe_budget one step finer, clamped to the ladder -- soft by one frame.  The factor 2 is a design constant (hysteresis wider
+ * than the step between neighbouring qualities), not a measurement.  I-frames, drop frames and failed calls leave the rung alone;
+ * pfv_encoder_set_rung may still be called and simply sets the state.  (Choosing an i-frame's rung by size needs a size probe; none exists yet.) */
+PFV_API int pfv_encoder_set_rate(pfv_encoder *e, uint32_t pframe_budget);
+
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);
  * every writer receives exactly the bytes an Encoder of its own would have written.  Per frame step: ONE upload of all

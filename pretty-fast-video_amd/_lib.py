@@ -157,6 +157,15 @@ SIGNATURES = [
     ("pfv_dec_distortion_dev", c_int, [_P, _P, _P, _P]),
     ("pfv_encoder_set_frame_report", c_int, [_P, c_int]),
     ("pfv_encoder_frame_report", c_int, [_P, _P]),
+    ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
+    ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
+    ("pfv_enc_session_rung", c_int, [_P]),
+    ("pfv_enc_session_rungs", c_int, [_P]),
+    ("pfv_encoder_create_ladder", c_int, [_P, c_int, c_int, c_int, _P, c_int, POINTER(_P)]),
+    ("pfv_encoder_set_rung", c_int, [_P, c_int]),
+    ("pfv_encoder_rung", c_int, [_P]),
+    ("pfv_encoder_rungs", c_int, [_P]),
+    ("pfv_encoder_set_rate", c_int, [_P, ctypes.c_uint32]),
     ("pfv_batch_encoder_create", c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(_P)]),
     ("pfv_batch_encoder_frames", _P, [_P]),
     ("pfv_batch_encoder_encode", c_int, [_P, c_int, _P]),

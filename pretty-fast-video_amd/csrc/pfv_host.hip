@@ -323,29 +323,32 @@ inline void emit_runs(std::vector<uint8_t> &payload, BitSink &w, const HuffmanTr
     }
 }
 
-// write_iframe_packet payload (enc.rs:237-320)
-inline bool serialize_iframe(std::vector<uint8_t> &payload, const int16_t *coef, int total_blocks)
+// write_iframe_packet payload (enc.rs:237-320).  qidx: the three q-table indices the packet names (a rung of a quality ladder); nullptr: the
+// reference's (0, 1, 1) / (2, 3, 3)
+inline bool serialize_iframe(std::vector<uint8_t> &payload, const int16_t *coef, int total_blocks, const uint8_t *qidx = nullptr)
 {
     BlockRuns br;
     if (!collect_runs(br, coef, nullptr, total_blocks)) return false;
     HuffmanTree tree(normalise_histogram(br.hist));
     BitSink w(payload);
     for (uint8_t t : tree.table()) w.put(8, t);
-    w.put(8, 0); w.put(8, 1); w.put(8, 1);   // q-table index per plane: intra_l, intra_c, intra_c (enc.rs:296-298)
+    static const uint8_t intra[3] = {0, 1, 1};   // q-table index per plane: intra_l, intra_c, intra_c (enc.rs:296-298)
+    for (int i = 0; i < 3; i++) w.put(8, (qidx ? qidx : intra)[i]);
     emit_runs(payload, w, tree, br);
     w.align();
     return true;
 }
 // write_pframe_packet payload (enc.rs:332-470)
 inline bool serialize_pframe(std::vector<uint8_t> &payload, const int8_t *mv, const uint8_t *has, const int16_t *coef,
-                             int total_blocks)
+                             int total_blocks, const uint8_t *qidx = nullptr)
 {
     BlockRuns br;
     if (!collect_runs(br, coef, has, total_blocks)) return false;
     HuffmanTree tree(normalise_histogram(br.hist));
     BitSink w(payload);
     for (uint8_t t : tree.table()) w.put(8, t);
-    w.put(8, 2); w.put(8, 3); w.put(8, 3);   // inter_l, inter_c, inter_c (enc.rs:409-411)
+    static const uint8_t inter[3] = {2, 3, 3};   // inter_l, inter_c, inter_c (enc.rs:409-411)
+    for (int i = 0; i < 3; i++) w.put(8, (qidx ? qidx : inter)[i]);
     for (int b = 0; b < total_blocks; b++) { // block headers, Y then U then V (enc.rs:414-451)
         bool has_mvec = mv[2 * b] != 0 || mv[2 * b + 1] != 0;
         w.put(1, has_mvec);

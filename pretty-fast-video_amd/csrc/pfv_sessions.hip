@@ -80,13 +80,16 @@ static bool enc_float_exact(const int32_t q[64], double amplitude)
     return worst < 8388608.0;   // 2^23: a factor 2 below what f32 holds exactly
 }
 
+constexpr int kMaxRungs = 11;   // qualities 0..10, strictly ascending
 struct pfv_enc_session {
     pfv_ctx *ctx = nullptr;
     int width = 0, height = 0, n_streams = 0;
     FrameGeom geom;
-    QTab *qtab_dev = nullptr;       // intra_l, intra_c, inter_l, inter_c
-    float px_err = 0.0f;
-    bool flt = false;                        // the closed loop may run in f32 (enc_float_exact holds for all four tables)
+    QTab *qtab_dev = nullptr;       // [4 * n_rungs], rung-major: intra_l, intra_c, inter_l, inter_c of each rung
+    int n_rungs = 1, rung = 0;               // quality ladder (pfv_enc_session_create_ladder); `rung` applies to the launches that follow
+    int qualities[kMaxRungs] = {0};
+    float px_err[kMaxRungs] = {0.0f};        // per rung
+    bool flt = false;                        // the closed loop may run in f32 (enc_float_exact holds for all tables of all rungs)
     int tile_compaction = 1;                 // PFV_OPT_TILE_COMPACTION at creation
     int lane_mapping = PFV_LANES_AUTO;       // PFV_OPT_LANE_MAPPING at creation
     uint8_t *prev[2] = {nullptr, nullptr};   // ping-pong prev_frame, padded, n_streams wide
@@ -146,34 +149,46 @@ static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
 
 extern "C" {
 
-PFV_API int pfv_enc_session_create(pfv_ctx *ctx, int width, int height, int quality, int n_streams,
-                                   pfv_enc_session **out)
+// qualities: n_rungs values in 0..10, strictly ascending (a higher quality number is a coarser quantiser, src/enc.rs:40-51).  Rung r holds
+// the four tables and the px_err of qualities[r], from the derivation of pfv_qtables_from_quality.
+PFV_API int pfv_enc_session_create_ladder(pfv_ctx *ctx, int width, int height, const int *qualities, int n_rungs, int n_streams,
+                                          pfv_enc_session **out)
 {
     if (!ctx || !out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_create: bad argument");
     *out = nullptr;
     if (width <= 0 || height <= 0 || (width & 1) || (height & 1) || width > 65535 || height > 65535)
         return fail(ctx, PFV_ERR_BAD_ARG, "width/height must be even (src/frame.rs:13) and fit u16 (src/enc.rs:195-196)");
-    if (quality < 0 || quality > 10) return fail(ctx, PFV_ERR_BAD_ARG, "quality must be in 0..10 (src/enc.rs:38)");
+    if (!qualities || n_rungs < 1 || n_rungs > kMaxRungs) return fail(ctx, PFV_ERR_BAD_ARG, "a quality ladder has 1..11 rungs");
+    for (int r = 0; r < n_rungs; r++) {
+        if (qualities[r] < 0 || qualities[r] > 10) return fail(ctx, PFV_ERR_BAD_ARG, "quality must be in 0..10 (src/enc.rs:38)");
+        if (r && qualities[r] <= qualities[r - 1]) return fail(ctx, PFV_ERR_BAD_ARG, "the qualities of a ladder must be strictly ascending");
+    }
     if (n_streams <= 0) return fail(ctx, PFV_ERR_BAD_ARG, "n_streams must be positive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     pfv_enc_session *s = new pfv_enc_session();
     s->ctx = ctx; s->width = width; s->height = height; s->n_streams = n_streams;
     s->win_count = n_streams;
     s->geom = frame_geom(width, height, n_streams);
-    int32_t q[4][64];
-    pfv_qtables_from_quality(quality, q[0], q[1], q[2], q[3], &s->px_err);
-    QTab tabs[4];
-    for (int i = 0; i < 4; i++) {
-        int rc = make_qtab(ctx, q[i], &tabs[i]);
-        if (rc) { delete s; return rc; }
+    s->n_rungs = n_rungs;
+    std::vector<QTab> tabs((size_t)4 * n_rungs);
+    bool exact = true;
+    for (int r = 0; r < n_rungs; r++) {
+        int32_t q[4][64];
+        s->qualities[r] = qualities[r];
+        pfv_qtables_from_quality(qualities[r], q[0], q[1], q[2], q[3], &s->px_err[r]);
+        for (int i = 0; i < 4; i++) {
+            int rc = make_qtab(ctx, q[i], &tabs[(size_t)4 * r + i]);
+            if (rc) { delete s; return rc; }
+        }
+        exact = exact && enc_float_exact(q[0], 128.0 * 256.0) && enc_float_exact(q[1], 128.0 * 256.0) && enc_float_exact(q[2], 127.0 * 256.0) &&
+                enc_float_exact(q[3], 127.0 * 256.0);
     }
     s->tile_compaction = ctx->opt_tile_compaction;
     s->lane_mapping = ctx->opt_lane_mapping;
-    s->flt = ctx->opt_enc_transform != PFV_ENC_TRANSFORM_INT && enc_float_exact(q[0], 128.0 * 256.0) && enc_float_exact(q[1], 128.0 * 256.0) &&
-             enc_float_exact(q[2], 127.0 * 256.0) && enc_float_exact(q[3], 127.0 * 256.0);
+    s->flt = ctx->opt_enc_transform != PFV_ENC_TRANSFORM_INT && exact;
     size_t pad_bytes = (size_t)s->geom.pad_frame_bytes * n_streams;
-    hipError_t e = hipMalloc((void **)&s->qtab_dev, sizeof tabs);
-    if (e == hipSuccess) e = hipMemcpy(s->qtab_dev, tabs, sizeof tabs, hipMemcpyHostToDevice);
+    hipError_t e = hipMalloc((void **)&s->qtab_dev, tabs.size() * sizeof(QTab));
+    if (e == hipSuccess) e = hipMemcpy(s->qtab_dev, tabs.data(), tabs.size() * sizeof(QTab), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&s->prev[0], pad_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&s->prev[1], pad_bytes);
     if (e != hipSuccess) {
@@ -188,6 +203,21 @@ PFV_API int pfv_enc_session_create(pfv_ctx *ctx, int width, int height, int qual
     *out = s;
     return PFV_OK;
 }
+// the one-rung ladder
+PFV_API int pfv_enc_session_create(pfv_ctx *ctx, int width, int height, int quality, int n_streams,
+                                   pfv_enc_session **out)
+{
+    return pfv_enc_session_create_ladder(ctx, width, height, &quality, 1, n_streams, out);
+}
+PFV_API int pfv_enc_session_set_rung(pfv_enc_session *s, int rung)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    if (rung < 0 || rung >= s->n_rungs) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_rung: rung outside the ladder");
+    s->rung = rung;
+    return PFV_OK;
+}
+PFV_API int pfv_enc_session_rung(pfv_enc_session *s) { return s ? s->rung : PFV_ERR_BAD_ARG; }
+PFV_API int pfv_enc_session_rungs(pfv_enc_session *s) { return s ? s->n_rungs : PFV_ERR_BAD_ARG; }
 
 PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
 {
@@ -237,13 +267,14 @@ static int enc_launch(pfv_enc_session *s, bool pframe, int first, int count, con
     FrameGeom g = enc_win_geom(s, count, src);
     if (slots_dev) g.src_slots = slots_dev + first;
     const int nxt = s->cur ^ 1;
+    const QTab *rung_tabs = s->qtab_dev + 4 * s->rung;           // the rung of this launch: its four tables, its px_err
     if (pframe) {
-        const float min_err = s->px_err * s->px_err * 256.0f;   // src/common.rs:209
+        const float min_err = s->px_err[s->rung] * s->px_err[s->rung] * 256.0f;   // src/common.rs:209
         launch_enc_pframe(ctx, s->flt, use_small_grid(s->lane_mapping, g), s->tile_compaction, g, src, s->prev[s->cur] + pad0, mv_dev + mb0 * 2,
-                          has_dev + mb0, coef_dev + mb0 * 256, s->prev[nxt] + pad0, s->qtab_dev + 2, min_err);
+                          has_dev + mb0, coef_dev + mb0 * 256, s->prev[nxt] + pad0, rung_tabs + 2, min_err);
         return launch_check(ctx, "k_enc_pframe");
     }
-    launch_enc_iframe(ctx, s->flt, use_small_grid(s->lane_mapping, g), g, src, coef_dev + mb0 * 256, s->prev[nxt] + pad0, s->qtab_dev + 0);
+    launch_enc_iframe(ctx, s->flt, use_small_grid(s->lane_mapping, g), g, src, coef_dev + mb0 * 256, s->prev[nxt] + pad0, rung_tabs + 0);
     return launch_check(ctx, "k_enc_iframe");
 }
 
@@ -417,8 +448,8 @@ static int ent_pack_win(pfv_enc_session *s, bool pframe, int first, int count, c
     f.pframe = pframe ? 1 : 0;
     f.cap_bytes = s->ent_cap;
     f.ones16 = 0x00010001u;
-    f.qidx[0] = pframe ? 2 : 0;                    // intra_l, intra_c, intra_c / inter_l, inter_c, inter_c
-    f.qidx[1] = f.qidx[2] = pframe ? 3 : 1;        // (enc.rs:296-298, :409-411)
+    f.qidx[0] = (uint8_t)(4 * s->rung + (pframe ? 2 : 0));                    // intra_l, intra_c, intra_c / inter_l, inter_c, inter_c
+    f.qidx[1] = f.qidx[2] = (uint8_t)(4 * s->rung + (pframe ? 3 : 1));        // (enc.rs:296-298, :409-411), of the current rung
     const size_t k = (size_t)first, tb = (size_t)f.total_blocks, ng = (size_t)f.n_groups;
     EntBufs b = s->ent;
     b.coef = coef_dev + k * tb * 256;

@@ -60,6 +60,9 @@ struct pfv_encoder {
     int report_state = 0;                  // 0: no encode_* call yet, 1: `report` describes the last one, -1: the last one failed
     pfv_frame_report report{};
     PinnedBuf<uint64_t> sums;              // [3]
+    // quality ladder (pfv_encoder_create_ladder): the current rung is the session's; rate control (pfv_encoder_set_rate)
+    int last_rung = -1;                    // rung of the last frame written (-1: none yet)
+    uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -358,14 +361,15 @@ static void put_packet(std::vector<uint8_t> &o, uint8_t type, const std::vector<
 
 extern "C" {
 
-// Encoder::new (src/enc.rs:37-73): q-tables from quality, prev_frame = new_padded, write_header (:190-219)
-PFV_API int pfv_encoder_create(pfv_ctx *ctx, int width, int height, int framerate, int quality, pfv_encoder **out)
+// Encoder::new (src/enc.rs:37-73): q-tables from quality, prev_frame = new_padded, write_header (:190-219) -- for a ladder of qualities: the
+// header carries 4 * n_rungs tables, rung-major, each rung in the order intra_l, intra_c, inter_l, inter_c
+PFV_API int pfv_encoder_create_ladder(pfv_ctx *ctx, int width, int height, int framerate, const int *qualities, int n_rungs, pfv_encoder **out)
 {
     if (!ctx || !out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_create: bad argument");
     *out = nullptr;
     if (framerate < 0 || framerate > 65535) return fail(ctx, PFV_ERR_BAD_ARG, "framerate must fit u16 (src/enc.rs:197)");
     pfv_enc_session *hot = nullptr;
-    int rc = pfv_enc_session_create(ctx, width, height, quality, 1, &hot);
+    int rc = pfv_enc_session_create_ladder(ctx, width, height, qualities, n_rungs, 1, &hot);
     if (rc) return rc;
     pfv_encoder *e = new pfv_encoder();
     e->ctx = ctx; e->hot = hot; e->width = width; e->height = height; e->framerate = framerate;
@@ -374,16 +378,42 @@ PFV_API int pfv_encoder_create(pfv_ctx *ctx, int width, int height, int framerat
         pfv_encoder_destroy(e);
         return fail(ctx, PFV_ERR_NOMEM, "pfv_encoder_create: pinned staging");
     }
-    int32_t q[4][64];
-    pfv_qtables_from_quality(quality, q[0], q[1], q[2], q[3], nullptr);
     static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};      // common.rs:1
     e->out.insert(e->out.end(), magic, magic + 8);
     put_u32(e->out, 211);                                                      // common.rs:2
     put_u16(e->out, (unsigned)width); put_u16(e->out, (unsigned)height); put_u16(e->out, (unsigned)framerate);
-    put_u16(e->out, 4);
-    for (int t = 0; t < 4; t++)                                                // intra_l, intra_c, inter_l, inter_c
-        for (int i = 0; i < 64; i++) put_u16(e->out, (unsigned)q[t][i]);
+    put_u16(e->out, 4u * (unsigned)n_rungs);
+    for (int r = 0; r < n_rungs; r++) {
+        int32_t q[4][64];
+        pfv_qtables_from_quality(qualities[r], q[0], q[1], q[2], q[3], nullptr);
+        for (int t = 0; t < 4; t++)                                            // intra_l, intra_c, inter_l, inter_c
+            for (int i = 0; i < 64; i++) put_u16(e->out, (unsigned)q[t][i]);
+    }
     *out = e;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_create(pfv_ctx *ctx, int width, int height, int framerate, int quality, pfv_encoder **out)
+{
+    return pfv_encoder_create_ladder(ctx, width, height, framerate, &quality, 1, out);
+}
+// the rung of the frames that follow, on both entropy paths
+PFV_API int pfv_encoder_set_rung(pfv_encoder *e, int rung)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    return pfv_enc_session_set_rung(e->hot, rung);
+}
+// the rung of the last frame written; before the first frame the current rung
+PFV_API int pfv_encoder_rung(pfv_encoder *e)
+{
+    if (!e) return PFV_ERR_BAD_ARG;
+    return e->last_rung >= 0 ? e->last_rung : e->hot->rung;
+}
+PFV_API int pfv_encoder_rungs(pfv_encoder *e) { return e ? e->hot->n_rungs : PFV_ERR_BAD_ARG; }
+// p-frame byte budget per payload, 0 = off; the rule is at the declaration (include/pfv_hip_ext.h) and in rate_frame_written
+PFV_API int pfv_encoder_set_rate(pfv_encoder *e, uint32_t pframe_budget)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    e->budget_p = pframe_budget;
     return PFV_OK;
 }
 
@@ -425,6 +455,16 @@ static int host_entropy_staging(pfv_encoder *e)
     return fail(e->ctx, PFV_ERR_NOMEM, "pinned staging for the host entropy path");
 }
 
+// a frame's packet has been written at the session's current rung with `payload_bytes` of payload
+static void rate_frame_written(pfv_encoder *e, bool pframe, size_t payload_bytes)
+{
+    pfv_enc_session *s = e->hot;
+    e->last_rung = s->rung;
+    if (!pframe || !e->budget_p) return;
+    if (payload_bytes > e->budget_p) s->rung = std::min(s->rung + 1, s->n_rungs - 1);
+    else if (2 * (uint64_t)payload_bytes <= e->budget_p) s->rung = std::max(s->rung - 1, 0);
+}
+
 // One frame through the device entropy stage: planes up, kernels, payload size then payload bytes down.
 static int encode_on_device(pfv_encoder *e, bool pframe)
 {
@@ -458,6 +498,7 @@ static int encode_on_device(pfv_encoder *e, bool pframe)
     put_u32(e->out, nbytes);
     e->out.insert(e->out.end(), e->payload.data(), e->payload.data() + nbytes);
     fill_report(e, pframe ? 2 : 1, 5 + (size_t)nbytes);
+    rate_frame_written(e, pframe, nbytes);
     return PFV_OK;
 }
 
@@ -504,11 +545,13 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     if ((rc = pfv_enc_iframe(e->hot, e->frame.data(), e->coef.data()))) return rc;
     e->poisoned = true;
     std::vector<uint8_t> payload;
-    if (!serialize_iframe(payload, e->coef.data(), e->total_blocks))
+    const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung), (uint8_t)(4 * e->hot->rung + 1), (uint8_t)(4 * e->hot->rung + 1)};
+    if (!serialize_iframe(payload, e->coef.data(), e->total_blocks, qidx))
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
     put_packet(e->out, 1, &payload);
     e->poisoned = false;
     fill_report(e, 1, 5 + payload.size());
+    rate_frame_written(e, false, payload.size());
     return PFV_OK;
 }
 // Encoder::encode_pframe (src/enc.rs:125-173)
@@ -526,11 +569,13 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
     if ((rc = pfv_enc_pframe(e->hot, e->frame.data(), e->mv.data(), e->has.data(), e->coef.data()))) return rc;
     e->poisoned = true;
     std::vector<uint8_t> payload;
-    if (!serialize_pframe(payload, e->mv.data(), e->has.data(), e->coef.data(), e->total_blocks))
+    const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung + 2), (uint8_t)(4 * e->hot->rung + 3), (uint8_t)(4 * e->hot->rung + 3)};
+    if (!serialize_pframe(payload, e->mv.data(), e->has.data(), e->coef.data(), e->total_blocks, qidx))
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
     put_packet(e->out, 2, &payload);
     e->poisoned = false;
     fill_report(e, 2, 5 + payload.size());
+    rate_frame_written(e, true, payload.size());
     return PFV_OK;
 }
 // Encoder::encode_dropframe (src/enc.rs:175-180): an i-frame packet with an empty payload

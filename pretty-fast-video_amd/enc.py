@@ -15,13 +15,20 @@ from .frame import VideoFrame
 
 
 class Encoder:
-    def __init__(self, writer, width: int, height: int, framerate: int, quality: int, ctx: Context, device_entropy: bool = True,
-                 frame_report: bool = False):
-        assert 0 <= quality <= 10                                   # src/enc.rs:38
+    def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
+                 frame_report: bool = False, qualities=None):
+        """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
+        quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame"""
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
         h = ctypes.c_void_p()
-        ctx.check(ctx._lib.pfv_encoder_create(ctx.handle, self.width, self.height, int(framerate), int(quality), ctypes.byref(h)))
+        if qualities is None:
+            assert 0 <= quality <= 10                               # src/enc.rs:38
+            ctx.check(ctx._lib.pfv_encoder_create(ctx.handle, self.width, self.height, int(framerate), int(quality), ctypes.byref(h)))
+        else:
+            assert quality is None, "give quality or qualities, not both"
+            q = (ctypes.c_int * len(qualities))(*[int(x) for x in qualities])
+            ctx.check(ctx._lib.pfv_encoder_create_ladder(ctx.handle, self.width, self.height, int(framerate), q, len(qualities), ctypes.byref(h)))
         self.handle = h
         # packet payloads from the device entropy stage (default) or the host serialisers: same bytes
         ctx.check(ctx._lib.pfv_encoder_set_device_entropy(h, 1 if device_entropy else 0))
@@ -62,6 +69,25 @@ class Encoder:
         assert not self.finished
         self.ctx.check(self.ctx._lib.pfv_encoder_encode_dropframe(self.handle))
         self._flush()
+
+    # quality ladder -------------------------------------------------------------------------------------------------
+    @property
+    def n_rungs(self) -> int:
+        return int(self.ctx._lib.pfv_encoder_rungs(self.handle))
+
+    def set_rung(self, rung: int):
+        """the rung of the frames that follow"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_rung(self.handle, int(rung)))
+
+    @property
+    def rung(self) -> int:
+        """the rung of the last frame written; before the first frame the current rung"""
+        return int(self.ctx._lib.pfv_encoder_rung(self.handle))
+
+    def set_rate(self, pframe_budget: int = 0):
+        """byte budget per p-frame payload (0: off): a p-frame over it moves the next frame one rung coarser, one at half the budget or
+        less one rung finer (pfv_encoder_set_rate)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_rate(self.handle, int(pframe_budget)))
 
     @property
     def last_report(self):

@@ -32,12 +32,20 @@ class _Geometry:
 
 
 class EncoderSession(_Geometry):
-    def __init__(self, ctx: Context, width: int, height: int, quality: int, n_streams: int = 1):
+    def __init__(self, ctx: Context, width: int, height: int, quality: int | None, n_streams: int = 1, qualities=None):
+        """``qualities=[...]`` (with ``quality=None``): a quality ladder, 1..11 values in 0..10, strictly ascending; ``set_rung`` picks the
+        rung of the launches that follow"""
         super().__init__(width, height, n_streams)
         self.ctx = ctx
         h = ctypes.c_void_p()
-        ctx.check(ctx._lib.pfv_enc_session_create(ctx.handle, int(width), int(height), int(quality), int(n_streams),
-                                                  ctypes.byref(h)))
+        if qualities is None:
+            ctx.check(ctx._lib.pfv_enc_session_create(ctx.handle, int(width), int(height), int(quality), int(n_streams),
+                                                      ctypes.byref(h)))
+        else:
+            assert quality is None, "give quality or qualities, not both"
+            q = (ctypes.c_int * len(qualities))(*[int(x) for x in qualities])
+            ctx.check(ctx._lib.pfv_enc_session_create_ladder(ctx.handle, int(width), int(height), q, len(qualities), int(n_streams),
+                                                             ctypes.byref(h)))
         self.handle = h
         ctx._sessions.add(self)
 
@@ -51,6 +59,19 @@ class EncoderSession(_Geometry):
             self.close()
         except Exception:
             pass
+
+    # quality ladder ----------------------------------------------------
+    @property
+    def n_rungs(self) -> int:
+        return int(self.ctx._lib.pfv_enc_session_rungs(self.handle))
+
+    @property
+    def rung(self) -> int:
+        return int(self.ctx._lib.pfv_enc_session_rung(self.handle))
+
+    def set_rung(self, rung: int):
+        """the rung of the encode / pack launches that follow (all slots of a launch share it)"""
+        self.ctx.check(self.ctx._lib.pfv_enc_session_set_rung(self.handle, int(rung)))
 
     # host-buffer forms ------------------------------------------------
     def _frames(self, frames) -> np.ndarray:
@@ -93,6 +114,7 @@ class EncoderSession(_Geometry):
 
     def set_window(self, first: int = 0, count: int | None = None):
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_window(self.handle, int(first), int(self.n_streams - first if count is None else count)))
+
 
     # device entropy stage (RLE + Huffman + bit packing of enc.rs:237-470 on the device) ---------------
     def enable_entropy(self, payload_cap: int = 0, async_stream: bool = False):
