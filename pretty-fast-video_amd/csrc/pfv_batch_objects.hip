@@ -54,7 +54,8 @@ static int be_collect(pfv_batch_encoder *b)
     if (rc) { b->poisoned = true; return rc; }
     for (int s = 0; s < b->n; s++) {
         const uint32_t nbytes = b->sizes[(size_t)s];
-        uint8_t head[5] = {(uint8_t)type, (uint8_t)nbytes, (uint8_t)(nbytes >> 8), (uint8_t)(nbytes >> 16), (uint8_t)(nbytes >> 24)};
+        uint8_t head[5];
+        put_packet_head(head, (uint8_t)type, nbytes);
         if (b->write) {   // packet header (src/enc.rs:301-305, :453-457) + payload as one write
             b->packet.assign(head, head + 5);
             b->packet.insert(b->packet.end(), b->payloads.data() + b->offsets[(size_t)s], b->payloads.data() + b->offsets[(size_t)s] + nbytes);
@@ -123,17 +124,8 @@ PFV_API int pfv_batch_encoder_create(pfv_ctx *ctx, int width, int height, int fr
     // landing zone for one step's payloads: typical content needs a fraction of the worst case; it grows on demand
     if (!rc && !b->payloads.resize(std::max<size_t>(in_bytes, 1 << 20))) rc = fail(ctx, PFV_ERR_NOMEM, "pinned payload staging");
     if (rc) { pfv_batch_encoder_destroy(b); return rc; }
-    // header (src/enc.rs:190-219): magic, version, geometry, the four q-tables -- to every writer
-    int32_t q[4][64];
-    pfv_qtables_from_quality(quality, q[0], q[1], q[2], q[3], nullptr);
-    std::vector<uint8_t> head;
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};
-    head.insert(head.end(), magic, magic + 8);
-    put_u32(head, 211);
-    put_u16(head, (unsigned)width); put_u16(head, (unsigned)height); put_u16(head, (unsigned)framerate);
-    put_u16(head, 4);
-    for (int t = 0; t < 4; t++)
-        for (int i = 0; i < 64; i++) put_u16(head, (unsigned)q[t][i]);
+    std::vector<uint8_t> head;                                                 // the header, to every writer
+    put_header(head, width, height, framerate, &quality, 1);
     for (int s = 0; s < n_streams; s++) be_emit(b, s, head.data(), head.size());
     *out = b;
     return PFV_OK;
@@ -191,8 +183,7 @@ PFV_API int pfv_batch_encoder_finish(pfv_batch_encoder *b)
     int rc = be_collect(b);
     if (rc) return rc;
     b->finished = true;
-    const uint8_t eof[5] = {0, 0, 0, 0, 0};                                    // src/enc.rs:221-227
-    for (int s = 0; s < b->n; s++) be_emit(b, s, eof, 5);
+    for (int s = 0; s < b->n; s++) be_emit(b, s, kPfvEof, sizeof kPfvEof);
     return PFV_OK;
 }
 // write == NULL at creation: the bytes produced for one stream since the last take (valid until the next call on `b`)
@@ -271,9 +262,7 @@ static void bd_parse_one(pfv_batch_decoder *b, BdSet *s, int k)
     SparseSink sink{s->idx.data() + (size_t)k * b->cap, s->val.data() + (size_t)k * b->cap, b->cap};
     sink.offset = (size_t)k * tb * 256;
     uint8_t *q = &s->qidx[(size_t)k * 3];
-    int rc = s->type == 2 ? parse_pframe_to(s->payload[(size_t)k], s->len[(size_t)k], (int)tb, b->n_qtables, s->mv.data() + (size_t)k * tb * 2,
-                                            s->has.data() + (size_t)k * tb, sink, q)
-                          : parse_iframe_to(s->payload[(size_t)k], s->len[(size_t)k], (int)tb, b->n_qtables, sink, q);
+    int rc = parse_frame_to(s->type, s->payload[(size_t)k], s->len[(size_t)k], (int)tb, b->n_qtables, s->mv.data() + (size_t)k * tb * 2, s->has.data() + (size_t)k * tb, sink, q);
     s->counts.data()[k] = (uint32_t)sink.n;
     s->rc[(size_t)k] = rc;
 }
@@ -305,21 +294,17 @@ static void bd_scan_and_start(pfv_batch_decoder *b, BdSet *s)
     for (int k = 0; k < b->n; k++) {
         const uint8_t *d = b->data[(size_t)k];
         size_t p = b->pos[(size_t)k];
-        int typ;
-        size_t n = 0;
-        for (;;) {
-            if (p + 5 > b->len[(size_t)k]) { s->type = PFV_ERR_IO; return; }
-            typ = d[p];
-            n = (size_t)d[p + 1] | ((size_t)d[p + 2] << 8) | ((size_t)d[p + 3] << 16) | ((size_t)d[p + 4] << 24);
-            if (typ == 0) break;
-            if (p + 5 + n > b->len[(size_t)k]) { s->type = PFV_ERR_IO; return; }
-            p += 5 + n;
-            if (typ == 1 || typ == 2) break;
-        }
+        PfvPacket pk;
+        do {   // up to the EOF marker (the stream stays in front of it) or behind the next frame packet
+            if (next_packet(d, b->len[(size_t)k], p, pk)) { s->type = PFV_ERR_IO; return; }
+            if (pk.type) p = pk.pos_after;
+        } while (pk.type > 2);
+        const int typ = pk.type;
+        const size_t n = pk.plen;
         b->pos[(size_t)k] = p;
         if (first < 0) first = typ;
         else if (typ != first) { s->type = PFV_ERR_FORMAT; return; }     // the streams' packet types diverge at this step
-        s->payload[(size_t)k] = typ ? d + p - n : nullptr;
+        s->payload[(size_t)k] = pk.payload;
         s->len[(size_t)k] = n;
         all_empty = all_empty && n == 0;
         any_empty = any_empty || n == 0;
@@ -366,72 +351,9 @@ static void bd_join(pfv_batch_decoder *b, BdSet *s)
 // cleared, k_entd_*, statuses down.
 static int bd_window_enqueue(pfv_batch_decoder *b, BdSet *s, DecWindow &w)
 {
-    pfv_ctx *ctx = b->ctx;
-    DecEntd &v = b->entd;
-    const size_t S = (size_t)b->n, tb = b->total_blocks;
-    int mrc = entd_windows_make(ctx, v, b->win, &b->win_stream, S, tb);
+    const int mrc = entd_windows_make(b->ctx, b->entd, b->win, &b->win_stream, (size_t)b->n, b->total_blocks);
     if (mrc) return mrc;
-    hipStream_t st = b->win_stream;
-    size_t total_sub = 0, n_groups = 0, hdr_total = 0;
-    unsigned max_hdr = 0;
-    for (size_t k = 0; k < S; k++) {
-        EdPacket &pk = s->pk.data()[k];
-        if (s->host_parse[k] || s->rc[k]) pk.n_sub = pk.hdr_wgs = 0;
-        pk.sub_first = (uint32_t)total_sub;
-        pk.grp_first = (uint32_t)n_groups;
-        pk.hdr_first = (uint32_t)hdr_total;
-        total_sub += pk.n_sub;
-        n_groups += (pk.n_sub + kEdOwn - 1) / kEdOwn;
-        hdr_total += pk.hdr_wgs;
-        max_hdr = std::max(max_hdr, (unsigned)pk.hdr_wgs);
-    }
-    if (total_sub >= 0xffffffffull) return fail(ctx, PFV_ERR_NOMEM, "batch decoder: payloads too large for one step of the device entropy stage");
-    if (!s->groups.resize(n_groups + 1)) return fail(ctx, PFV_ERR_NOMEM, "pinned staging");
-    {
-        size_t g = 0;
-        for (size_t k = 0; k < S; k++)
-            for (uint32_t blk = 0; blk * (uint32_t)kEdOwn < s->pk.data()[k].n_sub; blk++) s->groups.data()[g++] = make_uint2((unsigned)k, blk);
-    }
-    auto room = [&](auto **p, size_t *cap, size_t need) -> int {
-        if (need <= *cap) return PFV_OK;
-        if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }               // the set is idle: its last window was consumed and decoded
-        need += need / 2;
-        HIP_TRY(ctx, hipMalloc((void **)p, need * sizeof(**p)));
-        *cap = need;
-        return PFV_OK;
-    };
-    int rc;
-    if ((rc = room(&w.bytes_dev, &w.bytes_cap, s->bytes_total + 64))) return rc;
-    if ((rc = room(&w.groups_dev, &w.groups_cap, n_groups + 1))) return rc;
-    if ((rc = room(&w.sub_dev, &w.sub_cap, (total_sub + 1) * 4))) return rc;
-    if ((rc = room(&w.wgsum_dev, &w.wgsum_cap, n_groups + 1))) return rc;
-    if ((rc = room(&w.hdr_maps_dev, &w.hdr_maps_cap, (hdr_total + 1) * 8))) return rc;
-    if ((rc = room(&w.hdr_start_dev, &w.hdr_start_cap, hdr_total + 1))) return rc;
-    {   // every packet's list: its place in the window's pool from the packet's size
-        size_t total = 0;
-        w.list_room.assign(S, 0);
-        for (size_t k = 0; k < S; k++) { w.list_room[k] = entd_pool_cap(tb, s->len[k]); total += w.list_room[k]; }
-        w.lists.drop_spill();
-        if ((rc = w.lists.room(ctx, total))) return rc;
-        total = 0;
-        for (size_t k = 0; k < S; k++) { w.lists.ptr_host.data()[k] = w.lists.ent + total; total += w.list_room[k]; }
-        HIP_TRY(ctx, hipMemcpyAsync(w.lists.ptr_dev, w.lists.ptr_host.data(), S * sizeof(uint32_t *), hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(w.bytes_dev, s->bytes.data(), s->bytes_total, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(w.pk_dev, s->pk.data(), S * sizeof(EdPacket), hipMemcpyHostToDevice, st));
-    if (n_groups) HIP_TRY(ctx, hipMemcpyAsync(w.groups_dev, s->groups.data(), n_groups * sizeof(uint2), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(w.status_dev, 0, S * sizeof(uint32_t), st));
-    if (n_groups) {
-        const size_t ts = w.sub_cap / 4;
-        EdBufs eb{w.bytes_dev, w.pk_dev, w.groups_dev, w.sub_dev, w.sub_dev + ts, w.sub_dev + 2 * ts, w.wgsum_dev, w.coded_dev, w.lists.ptr_dev, w.lists.counts_dev, w.status_dev, 0u, 0u,
-                  w.hdr_maps_dev, w.hdr_start_dev, w.mv_dev, w.has_dev};
-        entd_launch(st, eb, (unsigned)S, (unsigned)n_groups, max_hdr, v.launches, v.inner);
-        if ((rc = launch_check(ctx, "k_entd_*"))) return rc;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(w.status_host.data(), w.status_dev, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipEventRecord(w.done, st));
-    w.owner = (DecEvent *)s;       // an identity only: which staging set this window belongs to
-    return PFV_OK;
+    return entd_window_enqueue(b->ctx, b->entd, w, b->win_stream, s->pk.data(), s->bytes.data(), s->bytes_total, s->len.data(), s->groups, s);
 }
 
 extern "C" {
@@ -458,30 +380,23 @@ PFV_API int pfv_batch_decoder_create(pfv_ctx *ctx, const uint8_t *const *streams
 {
     if (!ctx || !streams || !lens || !out || n_streams <= 0 || n_threads < 0) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_batch_decoder_create: bad argument");
     *out = nullptr;
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};
-    const uint8_t *d0 = streams[0];
-    if (!d0 || lens[0] < 8) return fail(ctx, PFV_ERR_IO, "stream shorter than the magic");
-    if (memcmp(d0, magic, 8) != 0) return fail(ctx, PFV_ERR_FORMAT, "bad magic (src/dec.rs:50-52)");
-    if (lens[0] < 20) return fail(ctx, PFV_ERR_IO, "truncated header");
-    const uint32_t ver = (uint32_t)d0[8] | ((uint32_t)d0[9] << 8) | ((uint32_t)d0[10] << 16) | ((uint32_t)d0[11] << 24);
-    if (ver != 211) return fail(ctx, PFV_ERR_VERSION, "codec version is not 2.1.1 (src/dec.rs:57-59)");
-    auto u16 = [&](size_t o) { return (int)d0[o] | ((int)d0[o + 1] << 8); };
-    const int w = u16(12), h = u16(14), fps = u16(16), nq = u16(18);
-    const size_t head = 20 + (size_t)nq * 128;
-    for (int k = 0; k < n_streams; k++) {
+    if (!streams[0]) return fail(ctx, PFV_ERR_IO, "stream shorter than the magic");
+    PfvHeader hd;
+    int rc = read_header(ctx, streams[0], lens[0], hd);
+    if (rc) return rc;
+    const int w = hd.width, h = hd.height, nq = hd.n_qtables;
+    const size_t head = hd.len;
+    for (int k = 1; k < n_streams; k++) {
         if (!streams[k] || lens[k] < head) return fail(ctx, PFV_ERR_IO, "truncated header");
-        if (memcmp(streams[k], d0, head) != 0) return fail(ctx, PFV_ERR_FORMAT, "the streams must share one header (geometry, frame rate, q-tables)");
+        if (memcmp(streams[k], streams[0], head) != 0) return fail(ctx, PFV_ERR_FORMAT, "the streams must share one header (geometry, frame rate, q-tables)");
     }
-    std::vector<int32_t> q((size_t)std::max(nq, 1) * 64, 1);
-    for (int i = 0; i < nq * 64; i++) q[(size_t)i] = u16(20 + 2 * (size_t)i);
     // the coefficient lists address [stream][macroblock][256] with 32-bit flat indices (SparseSink, k_scatter_coef_seg)
     if (w > 0 && h > 0 && !(w & 1) && !(h & 1) && (uint64_t)n_streams * (uint64_t)pfv_total_blocks(w, h) * 256u > 0xffffffffull)
         return fail(ctx, PFV_ERR_BAD_ARG, "pfv_batch_decoder_create: n_streams x macroblocks x 256 exceeds the 32-bit coefficient index; use several batch decoders");
     pfv_dec_session *hot = nullptr;
-    int rc = pfv_dec_session_create(ctx, w, h, q.data(), nq, n_streams, &hot);
-    if (rc) return rc;
+    if ((rc = pfv_dec_session_create(ctx, w, h, hd.q.data(), nq, n_streams, &hot))) return rc;
     pfv_batch_decoder *b = new pfv_batch_decoder();
-    b->ctx = ctx; b->hot = hot; b->n = n_streams; b->width = w; b->height = h; b->framerate = fps; b->n_qtables = nq;
+    b->ctx = ctx; b->hot = hot; b->n = n_streams; b->width = w; b->height = h; b->framerate = hd.framerate; b->n_qtables = nq;
     b->total_blocks = (size_t)pfv_total_blocks(w, h);
     b->frame_bytes = pfv_frame_bytes(w, h);
     b->cap = b->total_blocks * 256 / 4;                       // per stream: denser than 1 in 4 -> dense fallback
@@ -495,10 +410,8 @@ PFV_API int pfv_batch_decoder_create(pfv_ctx *ctx, const uint8_t *const *streams
         s.rc.assign(S, 0); s.qidx.assign(S * 3, 0); s.payload.assign(S, nullptr); s.len.assign(S, 0);
     }
     ok = ok && b->frames[0].resize(S * b->frame_bytes) && b->frames[1].resize(S * b->frame_bytes);
-    if (ok && ctx->opt_entropy_decode != PFV_ENTROPY_DECODE_HOST && tb > 0) {   // the steps' run streams are read on the device (big payloads; every step under _DEVICE)
-        DecEntd &v = b->entd;
-        v.force = ctx->opt_entropy_decode == PFV_ENTROPY_DECODE_DEVICE;
-        v.sub_bits = (uint32_t)ctx->opt_entdec_lane_bits; v.launches = ctx->opt_entdec_launches; v.inner = ctx->opt_entdec_inner;
+    DecEntd &v = b->entd;
+    if (entd_take_options(ctx, &v.force, &v.sub_bits, &v.launches, &v.inner) && ok && tb > 0) {   // the steps' run streams are read on the device (big payloads; every step under _DEVICE)
         bool host_ok = true;                // the window stream and sets: with the first step that takes the device form (bd_window_enqueue)
         for (auto &s : b->set) {
             host_ok = host_ok && s.pk.resize(S);
@@ -562,7 +475,7 @@ PFV_API int pfv_batch_decoder_advance(pfv_batch_decoder *b, const uint8_t **fram
     pfv_dec_session *hot = b->hot;
     const size_t total = tb * S * 256;
     int rc = PFV_OK;
-    if (s->dev_form && b->win[slot].owner != (DecEvent *)s && (rc = bd_window_enqueue(b, s, b->win[slot]))) {   // not enqueued ahead (first step, or its headers were late)
+    if (s->dev_form && b->win[slot].owner != s && (rc = bd_window_enqueue(b, s, b->win[slot]))) {   // not enqueued ahead (first step, or its headers were late)
         if (b->entd.ready || b->entd.force) return rc;
         // PFV_ENTROPY_DECODE_AUTO and the window stream / sets could not be made (they are created with the first step that takes the device
         // form): the stage is switched off for this decoder, this step is parsed by the host code here and now, the ones behind it on the pool
@@ -586,14 +499,7 @@ PFV_API int pfv_batch_decoder_advance(pfv_batch_decoder *b, const uint8_t **fram
             if (!s->host_parse[k] && !w.status_host.data()[k]) { v.packets_dev++; continue; }
             v.packets_host++;
             uint8_t q[3];
-            const int prc = b->hp.parse(s->payload[k], s->len[k], s->type, tb, b->n_qtables, s->mv.data() + k * tb * 2, s->has.data() + k * tb, w.list_room[k], q);
-            if (prc == PFV_ERR_NOMEM) return fail(ctx, prc, "pinned list staging");
-            if (prc) { b->eof = true; return fail(ctx, prc, "malformed packet payload"); }
-            if ((rc = upload_lists(ctx, w.lists, k, w.list_room[k], b->hp.ent.data(), b->hp.n, b->hp.counts.data(), ctx->stream))) return rc;
-            if (s->type == 2) {     // its block headers with it (the device's read of them is not what is decoded)
-                HIP_TRY(ctx, hipMemcpyAsync(w.mv_dev + k * tb * 2, s->mv.data() + k * tb * 2, tb * 2, hipMemcpyHostToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(w.has_dev + k * tb, s->has.data() + k * tb, tb, hipMemcpyHostToDevice, ctx->stream));
-            }
+            if ((rc = entd_host_parse(ctx, b->hp, w, k, s->payload[k], s->len[k], s->type, b->n_qtables, s->mv.data() + k * tb * 2, s->has.data() + k * tb, q, ctx->stream))) return rc;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                 // the one staging list is used again
         }
         rc = dec_step(hot, s->type == 2, w.mv_dev, w.has_dev, w.lists.coefs(), &s->qidx[0]);
@@ -625,8 +531,7 @@ PFV_API int pfv_batch_decoder_advance(pfv_batch_decoder *b, const uint8_t **fram
         for (size_t k = 0; k < S && !rc; k++) {
             DenseSink sink{b->dense.data() + k * tb * 256};
             uint8_t q[3];
-            rc = s->type == 2 ? parse_pframe_to(s->payload[k], s->len[k], (int)tb, b->n_qtables, s->mv.data() + k * tb * 2, s->has.data() + k * tb, sink, q)
-                              : parse_iframe_to(s->payload[k], s->len[k], (int)tb, b->n_qtables, sink, q);
+            rc = parse_frame_to(s->type, s->payload[k], s->len[k], (int)tb, b->n_qtables, s->mv.data() + k * tb * 2, s->has.data() + k * tb, sink, q);
         }
         if (rc) { b->eof = true; return fail(ctx, rc, "malformed packet payload"); }
         HIP_TRY(ctx, hipMemcpyAsync(hot->st_coef, b->dense.data(), total * 2, hipMemcpyHostToDevice, ctx->stream));

@@ -68,6 +68,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_plane_ops.hip"
 #include "pfv_sessions.hip"
 #include "pfv_quality.hip"
+#include "pfv_container.hip"
 #include "pfv_stream_objects.hip"
 #include "pfv_batch_objects.hip"
 #include "pfv_decoder_object.hip"

@@ -45,8 +45,7 @@ PFV_API int pfv_parse_payload_sparse(int is_pframe, const uint8_t *payload, size
     if (!payload || !idx_out || !val_out || !n_out || !qidx_out || total_blocks <= 0 || (is_pframe && (!mv_out || !has_coef_out)))
         return fail(nullptr, PFV_ERR_BAD_ARG, "pfv_parse_payload_sparse: bad argument");
     SparseSink sink{idx_out, val_out, cap};
-    int rc = is_pframe ? parse_pframe_to(payload, len, total_blocks, n_qtables, mv_out, has_coef_out, sink, qidx_out)
-                       : parse_iframe_to(payload, len, total_blocks, n_qtables, sink, qidx_out);
+    int rc = parse_frame_to(is_pframe ? 2 : 1, payload, len, total_blocks, n_qtables, mv_out, has_coef_out, sink, qidx_out);
     *n_out = sink.n;
     if (rc == kSinkFull) return 1;
     return rc ? fail(nullptr, rc, "malformed packet payload") : PFV_OK;
@@ -57,25 +56,16 @@ PFV_API int pfv_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len, pf
 {
     if (!ctx || !data || !out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_decoder_create: bad argument");
     *out = nullptr;
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};
-    if (len < 8) return fail(ctx, PFV_ERR_IO, "stream shorter than the magic (DecodeError::IOError)");
-    if (memcmp(data, magic, 8) != 0) return fail(ctx, PFV_ERR_FORMAT, "bad magic (DecodeError::FormatError, src/dec.rs:50-52)");
-    if (len < 12) return fail(ctx, PFV_ERR_IO, "truncated header");
-    uint32_t ver = (uint32_t)data[8] | ((uint32_t)data[9] << 8) | ((uint32_t)data[10] << 16) | ((uint32_t)data[11] << 24);
-    if (ver != 211) return fail(ctx, PFV_ERR_VERSION, "codec version is not 2.1.1 (DecodeError::VersionError, src/dec.rs:57-59)");
-    if (len < 20) return fail(ctx, PFV_ERR_IO, "truncated header");
-    auto u16 = [&](size_t o) { return (int)data[o] | ((int)data[o + 1] << 8); };
-    int w = u16(12), h = u16(14), fps = u16(16), nq = u16(18);
-    if (len < 20 + (size_t)nq * 128) return fail(ctx, PFV_ERR_IO, "truncated q-tables");
-    std::vector<int32_t> q((size_t)std::max(nq, 1) * 64, 1);
-    for (int i = 0; i < nq * 64; i++) q[i] = u16(20 + 2 * (size_t)i);
-    pfv_dec_session *hot = nullptr;
-    int rc = pfv_dec_session_create(ctx, w, h, q.data(), nq, 1, &hot);
+    PfvHeader hd;
+    int rc = read_header(ctx, data, len, hd);
     if (rc) return rc;
+    const int w = hd.width, h = hd.height;
+    pfv_dec_session *hot = nullptr;
+    if ((rc = pfv_dec_session_create(ctx, w, h, hd.q.data(), hd.n_qtables, 1, &hot))) return rc;
     pfv_decoder *d = new pfv_decoder();
     d->ctx = ctx; d->hot = hot; d->data = data; d->len = len;
-    d->pos = d->reset_pos = d->scan_pos = 20 + (size_t)nq * 128;
-    d->width = w; d->height = h; d->framerate = fps; d->n_qtables = nq;
+    d->pos = d->reset_pos = d->scan_pos = hd.len;
+    d->width = w; d->height = h; d->framerate = hd.framerate; d->n_qtables = hd.n_qtables;
     d->total_blocks = pfv_total_blocks(w, h);
     if (!d->retframe.resize(pfv_frame_bytes(w, h))) {
         pfv_decoder_destroy(d);
@@ -83,12 +73,8 @@ PFV_API int pfv_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len, pf
     }
     memset(d->retframe.data(), 0, (size_t)w * h);                              // VideoFrame::new (frame.rs:12-26): Y 0, U/V 128
     memset(d->retframe.data() + (size_t)w * h, 128, d->retframe.size() - (size_t)w * h);
-    if (ctx->opt_entropy_decode != PFV_ENTROPY_DECODE_HOST && d->total_blocks > 0) {   // the run streams of big packets are read on the device
-        DecEntd &v = d->entd;
-        v.force = ctx->opt_entropy_decode == PFV_ENTROPY_DECODE_DEVICE;
-        v.sub_bits = (uint32_t)ctx->opt_entdec_lane_bits; v.launches = ctx->opt_entdec_launches; v.inner = ctx->opt_entdec_inner;
-        v.on = true;                     // the window stream and sets: with the first packet that takes the device form (dec_window_enqueue)
-    }
+    // the run streams of big packets are read on the device; the window stream and sets: with the first packet that takes the device form (dec_window_enqueue)
+    d->entd.on = entd_take_options(ctx, &d->entd.force, &d->entd.sub_bits, &d->entd.launches, &d->entd.inner) && d->total_blocks > 0;
     const unsigned hw = std::thread::hardware_concurrency();
     if ((rc = pfv_decoder_set_lookahead(d, hw > 1 ? (int)std::min(4u, hw - 1) : 0))) {
         pfv_decoder_destroy(d);
@@ -106,10 +92,14 @@ static void dec_parse(pfv_decoder *d, DecEvent *e)   // any thread; touches only
     e->dense = false;
     e->n_sparse = 0;
     e->dev_form = e->host_parse = false;
+    auto parse_dense = [&]() -> int {
+        if (!e->coef.resize(tb * 256)) return PFV_ERR_NOMEM;
+        memset(e->coef.data(), 0, tb * 512);
+        DenseSink sink{e->coef.data()};
+        return parse_frame_to(e->type, e->payload, e->plen, d->total_blocks, d->n_qtables, e->mv.data(), e->has.data(), sink, e->qidx);
+    };
     if (d->entd.on && (d->entd.force || e->plen >= kDecEntdMinBytes)) {   // the device reads the run streams: only the headers here
-        const uint32_t max_sub = (uint32_t)(((uint64_t)e->plen * 8 + d->entd.sub_bits - 1) / d->entd.sub_bits);
-        if (!e->bytes.resize((size_t)e->plen + 32) || !e->pk.resize(1) || !e->groups.resize((size_t)max_sub / kEdOwn + 1) ||
-            (e->type == 2 && (!e->mv.resize(tb * 2) || !e->has.resize(tb)))) {
+        if (!e->bytes.resize((size_t)e->plen + 32) || !e->pk.resize(1) || (e->type == 2 && (!e->mv.resize(tb * 2) || !e->has.resize(tb)))) {
             e->rc = PFV_ERR_NOMEM;
             return;
         }
@@ -120,15 +110,10 @@ static void dec_parse(pfv_decoder *d, DecEvent *e)   // any thread; touches only
         memcpy(e->qidx, r.qidx, 3);
         e->dev_form = true;
         e->host_parse = r.host_parse;
-        if (r.rc || r.host_parse) k.n_sub = k.hdr_wgs = 0;
-        const uint32_t ng = (k.n_sub + kEdOwn - 1) / kEdOwn;
-        for (uint32_t g = 0; g < ng; g++) e->groups.data()[g] = make_uint2(0u, g);
         if (!e->rc && e->host_parse) {   // the host parser decides about this one, here, on this thread
-            if (!e->coef.resize(tb * 256)) { e->rc = PFV_ERR_NOMEM; return; }
-            e->rc = e->type == 1 ? parse_iframe(e->payload, e->plen, d->total_blocks, d->n_qtables, e->coef.data(), e->qidx)
-                                 : parse_pframe(e->payload, e->plen, d->total_blocks, d->n_qtables, e->mv.data(), e->has.data(), e->coef.data(), e->qidx);
             e->dev_form = false;
             e->dense = true;
+            e->rc = parse_dense();
         }
         return;
     }
@@ -137,19 +122,11 @@ static void dec_parse(pfv_decoder *d, DecEvent *e)   // any thread; touches only
         return;
     }
     SparseSink sink{e->idx.data(), e->val.data(), cap};
-    e->rc = e->type == 1 ? parse_iframe_to(e->payload, e->plen, d->total_blocks, d->n_qtables, sink, e->qidx)
-                         : parse_pframe_to(e->payload, e->plen, d->total_blocks, d->n_qtables, e->mv.data(), e->has.data(), sink,
-                                           e->qidx);
+    e->rc = parse_frame_to(e->type, e->payload, e->plen, d->total_blocks, d->n_qtables, e->mv.data(), e->has.data(), sink, e->qidx);
     e->n_sparse = sink.n;
     if (e->rc != kSinkFull) return;
     e->dense = true;
-    if (!e->coef.resize(tb * 256)) {
-        e->rc = PFV_ERR_NOMEM;
-        return;
-    }
-    e->rc = e->type == 1 ? parse_iframe(e->payload, e->plen, d->total_blocks, d->n_qtables, e->coef.data(), e->qidx)
-                         : parse_pframe(e->payload, e->plen, d->total_blocks, d->n_qtables, e->mv.data(), e->has.data(),
-                                        e->coef.data(), e->qidx);
+    e->rc = parse_dense();
 }
 static void dec_worker(pfv_decoder *d)
 {
@@ -178,42 +155,26 @@ static void dec_scan(pfv_decoder *d)
     bool queued = false;
     while (d->count < d->ring.size() && !d->scan_stop) {
         DecEvent *e = d->ring[(d->head + d->count) % d->ring.size()].get();
-        size_t pos = d->scan_pos;
         auto emit = [&](DecEvent::Kind kind, DecEvent::State st, size_t pos_after) {
             e->kind = kind; e->state = st; e->pos_after = pos_after;
             d->count++;
         };
-        if (pos + 5 > d->len) {
-            e->rc = PFV_ERR_IO; e->msg = "unexpected end of stream in a packet header";
-            emit(DecEvent::ERROR, DecEvent::DONE, pos);
+        PfvPacket pk;
+        const int rc = next_packet(d->data, d->len, d->scan_pos, pk);
+        if (rc || pk.type == 0) {   // the stream ends here, as it should (EOF marker, :183-187) or not
+            e->rc = rc; e->msg = pk.msg;
+            emit(rc ? DecEvent::ERROR : DecEvent::END, DecEvent::DONE, pk.pos_after);
             d->scan_stop = true;
             break;
         }
-        const uint8_t type = d->data[pos];
-        const uint32_t plen = (uint32_t)d->data[pos + 1] | ((uint32_t)d->data[pos + 2] << 8) | ((uint32_t)d->data[pos + 3] << 16) |
-                              ((uint32_t)d->data[pos + 4] << 24);
-        pos += 5;
-        if (type == 0) {   // EOF marker (:183-187)
-            emit(DecEvent::END, DecEvent::DONE, pos);
-            d->scan_stop = true;
-            break;
-        }
-        if (pos + plen > d->len) {
-            e->rc = PFV_ERR_IO; e->msg = "packet payload runs past the end of the stream";
-            emit(DecEvent::ERROR, DecEvent::DONE, pos);
-            d->scan_stop = true;
-            break;
-        }
-        const uint8_t *payload = d->data + pos;
-        pos += plen;
-        d->scan_pos = pos;
-        if (type != 1 && type != 2) continue;   // unknown packet: skipped (:216-219)
-        if (type == 1 && plen == 0) {           // drop frame: nothing decoded, no callback (:190)
-            emit(DecEvent::DROP, DecEvent::DONE, pos);
+        d->scan_pos = pk.pos_after;
+        if (pk.type != 1 && pk.type != 2) continue;   // unknown packet: skipped (:216-219)
+        if (pk.type == 1 && pk.plen == 0) {           // drop frame: nothing decoded, no callback (:190)
+            emit(DecEvent::DROP, DecEvent::DONE, pk.pos_after);
             continue;
         }
-        e->type = type; e->payload = payload; e->plen = plen; e->rc = 0;
-        emit(DecEvent::FRAME, DecEvent::QUEUED, pos);
+        e->type = pk.type; e->payload = pk.payload; e->plen = pk.plen; e->rc = 0;
+        emit(DecEvent::FRAME, DecEvent::QUEUED, pk.pos_after);
         queued = true;
     }
     if (queued) d->cv_work.notify_all();
@@ -310,49 +271,10 @@ PFV_API int pfv_decoder_reset(pfv_decoder *d)
 // The window of packet e on set w: uploads, cleared coefficient array, k_entd_*, status download -- all on the window stream.
 static int dec_window_enqueue(pfv_decoder *d, DecEvent *e, DecWindow &w)
 {
-    pfv_ctx *ctx = d->ctx;
-    DecEntd &v = d->entd;
-    const size_t tb = (size_t)d->total_blocks;
-    int mrc = entd_windows_make(ctx, v, d->win, &d->win_stream, 1, tb);
+    const int mrc = entd_windows_make(d->ctx, d->entd, d->win, &d->win_stream, 1, (size_t)d->total_blocks);
     if (mrc) return mrc;
-    hipStream_t st = d->win_stream;
-    const EdPacket &k = *e->pk.data();
-    const uint32_t ng = (k.n_sub + kEdOwn - 1) / kEdOwn;
-    auto room = [&](auto **p, size_t *cap, size_t need) -> int {
-        if (need <= *cap) return PFV_OK;
-        if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }           // the set is idle: its last window was consumed and decoded
-        need += need / 2;
-        HIP_TRY(ctx, hipMalloc((void **)p, need * sizeof(**p)));
-        *cap = need;
-        return PFV_OK;
-    };
-    int rc;
-    if ((rc = room(&w.bytes_dev, &w.bytes_cap, (size_t)e->plen + 64))) return rc;
-    if ((rc = room(&w.groups_dev, &w.groups_cap, (size_t)ng + 1))) return rc;
-    if ((rc = room(&w.sub_dev, &w.sub_cap, ((size_t)k.n_sub + 1) * 4))) return rc;
-    if ((rc = room(&w.wgsum_dev, &w.wgsum_cap, (size_t)ng + 1))) return rc;
-    if ((rc = room(&w.hdr_maps_dev, &w.hdr_maps_cap, ((size_t)k.hdr_wgs + 1) * 8))) return rc;
-    if ((rc = room(&w.hdr_start_dev, &w.hdr_start_cap, (size_t)k.hdr_wgs + 1))) return rc;
-    w.list_room.assign(1, entd_pool_cap(tb, e->plen));
-    w.lists.drop_spill();
-    if ((rc = w.lists.room(ctx, w.list_room[0]))) return rc;
-    w.lists.ptr_host.data()[0] = w.lists.ent;
-    HIP_TRY(ctx, hipMemcpyAsync(w.lists.ptr_dev, w.lists.ptr_host.data(), sizeof(uint32_t *), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(w.bytes_dev, e->bytes.data(), (size_t)e->plen + 16, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(w.pk_dev, e->pk.data(), sizeof(EdPacket), hipMemcpyHostToDevice, st));
-    if (ng) HIP_TRY(ctx, hipMemcpyAsync(w.groups_dev, e->groups.data(), ng * sizeof(uint2), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(w.status_dev, 0, sizeof(uint32_t), st));
-    if (ng) {
-        const size_t ts = w.sub_cap / 4;
-        EdBufs b{w.bytes_dev, w.pk_dev, w.groups_dev, w.sub_dev, w.sub_dev + ts, w.sub_dev + 2 * ts, w.wgsum_dev, w.coded_dev, w.lists.ptr_dev, w.lists.counts_dev, w.status_dev, 0u, 0u,
-                 w.hdr_maps_dev, w.hdr_start_dev, w.mv_dev, w.has_dev};
-        entd_launch(st, b, 1u, ng, k.hdr_wgs, v.launches, v.inner);
-        if ((rc = launch_check(ctx, "k_entd_*"))) return rc;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(w.status_host.data(), w.status_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipEventRecord(w.done, st));
-    w.owner = e;
-    return PFV_OK;
+    const size_t plen = e->plen;
+    return entd_window_enqueue(d->ctx, d->entd, w, d->win_stream, e->pk.data(), e->bytes.data(), plen + 16, &plen, e->groups, e);
 }
 // One packet through the device's entropy stage, then the decode launch; before the frame is fetched, the window of the
 // packet behind it -- if its headers are ready -- is put on the window stream, where it runs under this frame's decode and download.
@@ -362,7 +284,6 @@ static int dec_consume_entd(pfv_decoder *d, DecEvent *e)
     pfv_dec_session *hot = d->hot;
     DecEntd &v = d->entd;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t tb = (size_t)d->total_blocks;
     int rc;
     DecWindow *w = nullptr;
     for (DecWindow &x : d->win)
@@ -378,13 +299,7 @@ static int dec_consume_entd(pfv_decoder *d, DecEvent *e)
     if (*w->status_host.data()) {   // the device stage is not certain about this payload: the host parser reads it and decides
         v.packets_host++;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the staging list's last upload
-        const int prc = d->hp.parse(e->payload, e->plen, e->type, tb, d->n_qtables, e->mv.data(), e->has.data(), w->list_room[0], e->qidx);
-        if (prc) return fail(ctx, prc, prc == PFV_ERR_NOMEM ? "pinned list staging" : "malformed packet payload");
-        if ((rc = upload_lists(ctx, w->lists, 0, w->list_room[0], d->hp.ent.data(), d->hp.n, d->hp.counts.data(), ctx->stream))) return rc;
-        if (e->type == 2) {         // its block headers with it (the device's read of them is not what is decoded)
-            HIP_TRY(ctx, hipMemcpyAsync(w->mv_dev, e->mv.data(), tb * 2, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(w->has_dev, e->has.data(), tb, hipMemcpyHostToDevice, ctx->stream));
-        }
+        if ((rc = entd_host_parse(ctx, d->hp, *w, 0, e->payload, e->plen, e->type, d->n_qtables, e->mv.data(), e->has.data(), e->qidx, ctx->stream))) return rc;
     } else {
         v.packets_dev++;
     }

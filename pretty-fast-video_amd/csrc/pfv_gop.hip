@@ -129,19 +129,6 @@ static void gop_runs(const std::vector<int> &key, F &&fn)   // maximal runs of e
     }
 }
 
-static void gop_put_header(std::vector<uint8_t> &o, int width, int height, int framerate, int quality)
-{
-    int32_t q[4][64];
-    pfv_qtables_from_quality(quality, q[0], q[1], q[2], q[3], nullptr);
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};      // common.rs:1
-    o.insert(o.end(), magic, magic + 8);
-    put_u32(o, 211);                                                           // common.rs:2
-    put_u16(o, (unsigned)width); put_u16(o, (unsigned)height); put_u16(o, (unsigned)framerate);
-    put_u16(o, 4);
-    for (int t = 0; t < 4; t++)                                                // intra_l, intra_c, inter_l, inter_c (enc.rs:199-215)
-        for (int i = 0; i < 64; i++) put_u16(o, (unsigned)q[t][i]);
-}
-
 // the options of the caller's context as they stand now (the launches read them from the encoder's own)
 static void gop_enc_take_options(pfv_gop_encoder *e)
 {
@@ -335,7 +322,7 @@ static int gop_enc_collect(pfv_gop_encoder *e, GopEncBatch &B)
     if (!B.in_flight) {   // nothing was encoded: only drop frames can be pending
         gop_enc_materialize(e);
         for (const GopPacket &p : B.order)
-            if (p.type == 3) put_packet(e->out, 1, nullptr);
+            if (p.type == 3) put_packet(e->out, 1, nullptr, 0);
         B.clear();
         return PFV_OK;
     }
@@ -371,9 +358,8 @@ static int gop_enc_collect(pfv_gop_encoder *e, GopEncBatch &B)
         for (const GopPacket &p : B.order) {      // packets in stream order: 5 header bytes, then the payload where gop_enc_redo left it
             uint8_t *h = &B.heads[hi];
             hi += 5;
-            if (p.type == 3) { h[0] = 1; h[1] = h[2] = h[3] = h[4] = 0; e->segs.push_back(pfv_iovec{h, 5}); continue; }
-            const uint32_t size = e->redo_sizes[k++];
-            h[0] = p.type; h[1] = (uint8_t)size; h[2] = (uint8_t)(size >> 8); h[3] = (uint8_t)(size >> 16); h[4] = (uint8_t)(size >> 24);
+            const uint32_t size = p.type == 3 ? 0u : e->redo_sizes[k++];   // type 3, a drop frame: an empty i-frame packet (src/enc.rs:175-180)
+            put_packet_head(h, p.type == 3 ? 1 : p.type, size);
             e->segs.push_back(pfv_iovec{h, 5});
             if (size) e->segs.push_back(pfv_iovec{B.redo.data() + off, (size_t)size});
             off += size;
@@ -397,12 +383,12 @@ static int gop_enc_collect(pfv_gop_encoder *e, GopEncBatch &B)
         uint8_t *h = &B.heads[hi];
         hi += 5;
         if (p.type == 3) {                                                // drop frame: an empty i-frame packet (src/enc.rs:175-180)
-            h[0] = 1; h[1] = h[2] = h[3] = h[4] = 0;
+            put_packet_head(h, 1, 0);
             e->segs.push_back(pfv_iovec{h, 5});
             continue;
         }
         const EntEntry &en = e->entries_host.data()[(size_t)p.t * (size_t)e->max_gops + (size_t)p.slot];
-        h[0] = p.type; h[1] = (uint8_t)en.size; h[2] = (uint8_t)(en.size >> 8); h[3] = (uint8_t)(en.size >> 16); h[4] = (uint8_t)(en.size >> 24);
+        put_packet_head(h, p.type, en.size);
         e->segs.push_back(pfv_iovec{h, 5});
         if (en.size) e->segs.push_back(pfv_iovec{B.payload_host.data() + en.offset, (size_t)en.size});
     }
@@ -591,7 +577,7 @@ PFV_API int pfv_gop_encoder_create(pfv_ctx *ctx, int width, int height, int fram
     for (GopEncBatch &B : e->batch)
         if (!rc && !B.payload_host.resize(std::min(e->arena_cap, cap_frames * e->frame_bytes / 6 + ((size_t)16 << 10)))) rc = fail(ctx, PFV_ERR_NOMEM, "pinned payload staging");
     if (rc) { pfv_gop_encoder_destroy(e); return rc; }
-    gop_put_header(e->out, width, height, framerate, quality);               // write_header (src/enc.rs:190-219)
+    put_header(e->out, width, height, framerate, &quality, 1);
     *out = e;
     return PFV_OK;
 }
@@ -649,8 +635,7 @@ PFV_API int pfv_gop_encoder_finish(pfv_gop_encoder *e)
     int rc = pfv_gop_encoder_flush(e);
     if (rc) return rc;
     e->finished = true;
-    static const uint8_t eof[5] = {0, 0, 0, 0, 0};                               // src/enc.rs:221-227
-    e->segs.push_back(pfv_iovec{eof, 5});
+    e->segs.push_back(pfv_iovec{kPfvEof, sizeof kPfvEof});
     return PFV_OK;
 }
 PFV_API int pfv_gop_encoder_bytes(pfv_gop_encoder *e, const uint8_t **data, size_t *len)
@@ -842,9 +827,7 @@ static void gopd_parse_one(pfv_gop_decoder *d, GopDecSet *s, int k)
     SparseSink sink{s->idx.data() + (size_t)k * d->cap, s->val.data() + (size_t)k * d->cap, d->cap};
     sink.offset = (size_t)k * tb * 256;
     uint8_t *q = &s->qidx[(size_t)k * 3];
-    const int rc = e->type == 2 ? parse_pframe_to(e->payload, e->plen, (int)tb, d->n_qtables, s->mv.data() + (size_t)k * tb * 2,
-                                                  s->has.data() + (size_t)k * tb, sink, q)
-                                : parse_iframe_to(e->payload, e->plen, (int)tb, d->n_qtables, sink, q);
+    const int rc = parse_frame_to(e->type, e->payload, e->plen, (int)tb, d->n_qtables, s->mv.data() + (size_t)k * tb * 2, s->has.data() + (size_t)k * tb, sink, q);
     s->counts.data()[k] = rc == 0 ? (uint32_t)sink.n : 0u;
     s->rc[(size_t)k] = rc;
 }
@@ -934,21 +917,16 @@ static void gopd_scan_batch(pfv_gop_decoder *d)
         return e;
     };
     for (;;) {
-        if (pos + 5 > d->len) {
-            GopDecEvent &e = push(GopDecEvent::ERROR, pos);
-            e.rc = PFV_ERR_IO; e.msg = "unexpected end of stream in a packet header";
+        PfvPacket pk;
+        const int rc = next_packet(d->data, d->len, pos, pk);
+        if (rc || pk.type == 0) {   // the stream ends here, as it should (EOF marker, :183-187) or not
+            GopDecEvent &e = push(rc ? GopDecEvent::ERROR : GopDecEvent::END, pk.pos_after);
+            e.rc = rc; e.msg = pk.msg;
             break;
         }
-        const uint8_t type = d->data[pos];
-        const uint32_t plen = (uint32_t)d->data[pos + 1] | ((uint32_t)d->data[pos + 2] << 8) | ((uint32_t)d->data[pos + 3] << 16) |
-                              ((uint32_t)d->data[pos + 4] << 24);
-        if (type == 0) { push(GopDecEvent::END, pos + 5); break; }                  // EOF marker (:183-187)
-        if (pos + 5 + (size_t)plen > d->len) {
-            GopDecEvent &e = push(GopDecEvent::ERROR, pos + 5);
-            e.rc = PFV_ERR_IO; e.msg = "packet payload runs past the end of the stream";
-            break;
-        }
-        const size_t after = pos + 5 + (size_t)plen;
+        const uint8_t type = pk.type;
+        const uint32_t plen = pk.plen;
+        const size_t after = pk.pos_after;
         if (type != 1 && type != 2) { pos = after; continue; }                      // unknown packet: skipped (:216-219)
         if (type == 1 && plen == 0) { push(GopDecEvent::DROP, after); pos = after; continue; }   // drop frame (:190)
         if (type == 1) {
@@ -959,7 +937,7 @@ static void gopd_scan_batch(pfv_gop_decoder *d)
             d->glen.push_back(0); d->gfirst.push_back(2);
         }
         GopDecEvent &e = push(GopDecEvent::FRAME, after);
-        e.type = type; e.payload = d->data + pos + 5; e.plen = plen;
+        e.type = type; e.payload = pk.payload; e.plen = plen;
         e.slot = (int)d->glen.size() - 1; e.t = d->glen.back()++;
         pos = after;
     }
@@ -1169,9 +1147,7 @@ static int gopd_decode_batch(pfv_gop_decoder *d)
                 memset(d->dense.data(), 0, tb * 512);
                 DenseSink sink{d->dense.data()};
                 uint8_t q[3];
-                const int prc = e->type == 2 ? parse_pframe_to(e->payload, e->plen, (int)tb, d->n_qtables, s.mv.data() + (size_t)k * tb * 2,
-                                                               s.has.data() + (size_t)k * tb, sink, q)
-                                             : parse_iframe_to(e->payload, e->plen, (int)tb, d->n_qtables, sink, q);
+                const int prc = parse_frame_to(e->type, e->payload, e->plen, (int)tb, d->n_qtables, s.mv.data() + (size_t)k * tb * 2, s.has.data() + (size_t)k * tb, sink, q);
                 if (prc) {
                     e->rc = prc; e->msg = kBadPayload; key[(size_t)k] = -1;
                     HIP_TRY(ctx, hipMemcpyAsync(hot->fb[hot->cur ^ 1] + (size_t)k * pad, hot->fb[hot->cur] + (size_t)k * pad, pad, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1265,16 +1241,6 @@ static int gopd_dev_upload_headers(pfv_gop_decoder *d, const GopDevPacket &p)
     HIP_TRY(ctx, hipMemcpyAsync(v.has_dev + p.frame * tb, v.has_host.data() + p.frame * tb, tb, hipMemcpyHostToDevice, ctx->stream));
     return PFV_OK;
 }
-template <class T>
-static int gopd_dev_room(pfv_ctx *ctx, T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return PFV_OK;
-    if (*p) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    need += need / 4;
-    HIP_TRY(ctx, hipMalloc((void **)p, need * sizeof(T)));
-    *cap = need;
-    return PFV_OK;
-}
 
 // Decode the scanned batch with the payloads read on the device.  PFV_OK: done (frames in frames_host[step][slot]); 1: this batch needs
 // the host path (a group's i-frame does not parse: the chains change, see gopd_decode_batch) -- nothing has been decoded; negative: error.
@@ -1335,20 +1301,20 @@ static int gopd_decode_batch_dev(pfv_gop_decoder *d)
     if (sub_max >= 0xffffffffull) return 1;
     int rc = PFV_OK;
     if (!v.groups_host.resize(std::max<size_t>(grp_max, 1))) return fail(ctx, PFV_ERR_NOMEM, "device-entropy staging");
-    if ((rc = gopd_dev_room(ctx, &v.bytes_dev, &v.bytes_cap, bytes_total + 64))) return rc;
+    if ((rc = dev_room(ctx, &v.bytes_dev, &v.bytes_cap, bytes_total + 64, 4, &ctx->stream))) return rc;
     if (n > v.pk_cap) {
         if (v.pk_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(v.pk_dev); (void)hipFree(v.status_dev); v.pk_dev = nullptr; v.status_dev = nullptr; v.pk_cap = 0; }
         HIP_TRY(ctx, hipMalloc((void **)&v.pk_dev, (n + n / 4) * sizeof(EdPacket)));
         HIP_TRY(ctx, hipMalloc((void **)&v.status_dev, (n + n / 4) * sizeof(uint32_t)));
         v.pk_cap = n + n / 4;
     }
-    if ((rc = gopd_dev_room(ctx, &v.groups_dev, &v.groups_cap, std::max<size_t>(grp_max, 1)))) return rc;
-    if ((rc = gopd_dev_room(ctx, &v.sub_dev, &v.sub_cap, std::max<size_t>(sub_max, 1) * 4))) return rc;
-    if ((rc = gopd_dev_room(ctx, &v.wgsum_dev, &v.wgsum_cap, std::max<size_t>(grp_max, 1)))) return rc;
+    if ((rc = dev_room(ctx, &v.groups_dev, &v.groups_cap, std::max<size_t>(grp_max, 1), 4, &ctx->stream))) return rc;
+    if ((rc = dev_room(ctx, &v.sub_dev, &v.sub_cap, std::max<size_t>(sub_max, 1) * 4, 4, &ctx->stream))) return rc;
+    if ((rc = dev_room(ctx, &v.wgsum_dev, &v.wgsum_cap, std::max<size_t>(grp_max, 1), 4, &ctx->stream))) return rc;
     size_t hdr_max = 0;
     for (size_t j = 0; j < n; j++) hdr_max += v.pk[j].ev->type == 2 ? entd_hdr_wgs(tb, v.pk[j].ev->plen) : 0;
-    if ((rc = gopd_dev_room(ctx, &v.hdr_maps_dev, &v.hdr_maps_cap, (hdr_max + 1) * 8))) return rc;
-    if ((rc = gopd_dev_room(ctx, &v.hdr_start_dev, &v.hdr_start_cap, hdr_max + 1))) return rc;
+    if ((rc = dev_room(ctx, &v.hdr_maps_dev, &v.hdr_maps_cap, (hdr_max + 1) * 8, 4, &ctx->stream))) return rc;
+    if ((rc = dev_room(ctx, &v.hdr_start_dev, &v.hdr_start_cap, hdr_max + 1, 4, &ctx->stream))) return rc;
     // the coefficient lists: every packet's place in the pool from its size alone (entd_pool_cap), the frames' list pointers with them
     v.list_off.assign(n, 0); v.list_room.assign(n, 0);
     size_t list_total = 0;
@@ -1382,7 +1348,7 @@ static int gopd_decode_batch_dev(pfv_gop_decoder *d)
         d->cv_work.notify_all();
     }
     const size_t ts = v.sub_cap / 4;
-    size_t total_sub = 0, n_groups = 0, hdr_total = 0;
+    EntdTotals nt;                       // subsequences, workgroups and header workgroups of the windows enqueued so far
     int next_window = 0;
     // the windows of steps [next_window, upto]: uploads and clears on one stream, the kernels behind them on another
     auto windows_upto = [&](int upto) -> int {
@@ -1391,20 +1357,9 @@ static int gopd_decode_batch_dev(pfv_gop_decoder *d)
             GopClock wclk;
             gopd_join(d, &v.step_pending[(size_t)t]);
             d->stats[1] += wclk.lap();
-            const size_t f0 = (size_t)t * S, pa = p0[(size_t)t], pb = p0[(size_t)t + 1], ga = n_groups;
-            unsigned max_hdr = 0;
-            for (size_t j = pa; j < pb; j++) {
-                EdPacket &k = v.pk_host.data()[j];
-                if (v.pk[j].rc || v.pk[j].host_parse) k.n_sub = k.hdr_wgs = 0;
-                k.sub_first = (uint32_t)total_sub;
-                k.grp_first = (uint32_t)n_groups;
-                k.hdr_first = (uint32_t)hdr_total;
-                hdr_total += k.hdr_wgs;
-                max_hdr = std::max(max_hdr, (unsigned)k.hdr_wgs);
-                total_sub += k.n_sub;
-                for (uint32_t b = 0; b * (uint32_t)kEdOwn < k.n_sub; b++) v.groups_host.data()[n_groups++] = make_uint2((unsigned)j, b);
-            }
-            const size_t gb = n_groups, ba = byte0[(size_t)t], bb = byte0[(size_t)t + 1];
+            const size_t pa = p0[(size_t)t], pb = p0[(size_t)t + 1], ga = nt.groups;
+            const unsigned max_hdr = entd_number(v.pk_host.data(), pa, pb, v.groups_host.data(), nt);
+            const size_t gb = nt.groups, ba = byte0[(size_t)t], bb = byte0[(size_t)t + 1];
             if (pb > pa) HIP_TRY(ctx, hipMemcpyAsync(v.pk_dev + pa, v.pk_host.data() + pa, (pb - pa) * sizeof(EdPacket), hipMemcpyHostToDevice, v.up_stream));
             if (gb > ga) HIP_TRY(ctx, hipMemcpyAsync(v.groups_dev + ga, v.groups_host.data() + ga, (gb - ga) * sizeof(uint2), hipMemcpyHostToDevice, v.up_stream));
             if (bb > ba) HIP_TRY(ctx, hipMemcpyAsync(v.bytes_dev + ba, v.bytes_host.data() + ba, bb - ba, hipMemcpyHostToDevice, v.up_stream));
@@ -1585,27 +1540,18 @@ PFV_API int pfv_gop_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len
     *out = nullptr;
     if (max_gops <= 0 || max_gop_frames <= 0 || max_gops > 4096 || max_gop_frames > 4096 || n_threads < 0 || n_threads > 256)
         return fail(ctx, PFV_ERR_BAD_ARG, "pfv_gop_decoder_create: max_gops and max_gop_frames must be in 1..4096, n_threads in 0..256");
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};
-    if (len < 8) return fail(ctx, PFV_ERR_IO, "stream shorter than the magic (DecodeError::IOError)");
-    if (memcmp(data, magic, 8) != 0) return fail(ctx, PFV_ERR_FORMAT, "bad magic (DecodeError::FormatError, src/dec.rs:50-52)");
-    if (len < 12) return fail(ctx, PFV_ERR_IO, "truncated header");
-    const uint32_t ver = (uint32_t)data[8] | ((uint32_t)data[9] << 8) | ((uint32_t)data[10] << 16) | ((uint32_t)data[11] << 24);
-    if (ver != 211) return fail(ctx, PFV_ERR_VERSION, "codec version is not 2.1.1 (DecodeError::VersionError, src/dec.rs:57-59)");
-    if (len < 20) return fail(ctx, PFV_ERR_IO, "truncated header");
-    auto u16 = [&](size_t o) { return (int)data[o] | ((int)data[o + 1] << 8); };
-    const int w = u16(12), h = u16(14), fps = u16(16), nq = u16(18);
-    if (len < 20 + (size_t)nq * 128) return fail(ctx, PFV_ERR_IO, "truncated q-tables");
-    std::vector<int32_t> q((size_t)std::max(nq, 1) * 64, 1);
-    for (int i = 0; i < nq * 64; i++) q[(size_t)i] = u16(20 + 2 * (size_t)i);
+    PfvHeader hd;
+    int rc = read_header(ctx, data, len, hd);
+    if (rc) return rc;
+    const int w = hd.width, h = hd.height, nq = hd.n_qtables;
     if (w > 0 && h > 0 && !(w & 1) && !(h & 1) && (uint64_t)max_gops * (uint64_t)pfv_total_blocks(w, h) * 256u > 0xffffffffull)
         return fail(ctx, PFV_ERR_BAD_ARG, "pfv_gop_decoder_create: max_gops x macroblocks x 256 exceeds the 32-bit coefficient index");
     pfv_dec_session *hot = nullptr;
-    int rc = pfv_dec_session_create(ctx, w, h, q.data(), nq, max_gops, &hot);
-    if (rc) return rc;
+    if ((rc = pfv_dec_session_create(ctx, w, h, hd.q.data(), nq, max_gops, &hot))) return rc;
     pfv_gop_decoder *d = new pfv_gop_decoder();
     d->ctx = ctx; d->hot = hot; d->data = data; d->len = len;
-    d->pos = d->reset_pos = 20 + (size_t)nq * 128;
-    d->width = w; d->height = h; d->framerate = fps; d->n_qtables = nq; d->max_gops = max_gops; d->max_len = max_gop_frames;
+    d->pos = d->reset_pos = hd.len;
+    d->width = w; d->height = h; d->framerate = hd.framerate; d->n_qtables = nq; d->max_gops = max_gops; d->max_len = max_gop_frames;
     d->total_blocks = (size_t)pfv_total_blocks(w, h);
     d->frame_bytes = pfv_frame_bytes(w, h);
     d->cap = d->total_blocks * 256 / 4;                        // per slot: denser than 1 non-zero in 4 -> dense fallback
@@ -1630,15 +1576,16 @@ PFV_API int pfv_gop_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len
     if (!rc) rc = dec_staging(hot);
     if (!rc) rc = pfv_dec_set_output_dev(hot, d->frames_dev);
     // the device-entropy path keeps the coefficient arrays of a whole batch in HBM (PFV_OPT_ENTROPY_DECODE)
-    if (!rc && ctx->opt_entropy_decode != PFV_ENTROPY_DECODE_HOST && tb > 0) {
-        GopDecDev &v = d->dev;
+    GopDecDev &v = d->dev;
+    bool force = false;
+    if (entd_take_options(ctx, &force, &v.sub_bits, &v.launches, &v.inner) && !rc && tb > 0) {
         const size_t F = S * (size_t)max_gop_frames;
         // per frame: motion vectors, flags, coded list, counts; the coefficient lists at 4 bytes per 3 payload bits at most (entd_pool_cap)
         const size_t list_guess = std::min(std::min(len, F * (tb * 512 / 8 + 64)) * 8 / 3 + F * 4, F * tb * 256);
         const size_t need = F * tb * (2 + 1 + 4 + 4 + 64) + list_guess * 4;
         size_t free_b = 0, total_b = 0;
         bool fits = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < free_b / 2;
-        if (ctx->opt_entropy_decode == PFV_ENTROPY_DECODE_DEVICE) fits = true;
+        if (force) fits = true;
         if (fits) {
             hipError_t e2 = hipSuccess;
             if (getenv("PFV_GOPD_WINDOW_STREAMS")) v.n_streams = std::max(1, std::min((int)GopDecDev::kStreams, atoi(getenv("PFV_GOPD_WINDOW_STREAMS"))));   // experiments
@@ -1650,7 +1597,6 @@ PFV_API int pfv_gop_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len
             if (e2 == hipSuccess) e2 = hipMalloc((void **)&v.coded_dev, F * tb * 4);
             // a batch's payloads are at most the whole stream: size the staging now, not inside the first batch
             const size_t bytes_guess = std::min(len + F * 32 + 64, F * (tb * 512 / 8 + 64));
-            v.sub_bits = (uint32_t)ctx->opt_entdec_lane_bits; v.launches = ctx->opt_entdec_launches; v.inner = ctx->opt_entdec_inner;   // PFV_OPT_ENTDEC_*
             const size_t sub_guess = bytes_guess * 8 / v.sub_bits + F;
             if (e2 == hipSuccess) e2 = hipMalloc((void **)&v.bytes_dev, bytes_guess);
             if (e2 == hipSuccess) { v.bytes_cap = bytes_guess; e2 = hipMalloc((void **)&v.sub_dev, sub_guess * 4 * sizeof(uint32_t)); }
@@ -1676,7 +1622,7 @@ PFV_API int pfv_gop_decoder_create(pfv_ctx *ctx, const uint8_t *data, size_t len
                 for (hipStream_t &st : v.streams)
                     if (st) { (void)hipStreamDestroy(st); st = nullptr; }
                 if (v.up_stream) { (void)hipStreamDestroy(v.up_stream); v.up_stream = nullptr; }
-                if (ctx->opt_entropy_decode == PFV_ENTROPY_DECODE_DEVICE)
+                if (force)
                     rc = fail(ctx, PFV_ERR_NOMEM, "pfv_gop_decoder_create: the batch's coefficient arrays do not fit the device (PFV_ENTROPY_DECODE_DEVICE): use a smaller batch");
             }
         }

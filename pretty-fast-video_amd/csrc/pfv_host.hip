@@ -1,5 +1,5 @@
 // pfv_host.hip -- host half of the drop-in: pfv::Encoder / pfv::Decoder session objects with the reference's
-// surface (src/enc.rs:12-188, src/dec.rs:15-224), the .pfv container (src/enc.rs:190-235, src/dec.rs:38-118) and
+// surface (src/enc.rs:12-188, src/dec.rs:15-224) -- the .pfv container is pfv_container.hip's -- and
 // the host-side entropy layer (src/rle.rs, src/huffman.rs, src/enc.rs:237-481, src/dec.rs:226-448).  Entropy
 // coding is serial, bit-granular work and stays on the host by design (BASELINE.json north_star); everything
 // per-macroblock goes through the device sessions of pfv_capi.hip.  Included by pfv_capi.hip (one translation
@@ -572,6 +572,12 @@ inline int parse_pframe_to(const uint8_t *payload, size_t n, int total_blocks, i
         if (has[b])
             if (int rc = read_runs(r, tree, sink, (size_t)b * 256, 256)) return rc;
     return 0;
+}
+// a frame packet of either type (1 = i-frame, 2 = p-frame: mv / has are only written then)
+template <class Sink>
+inline int parse_frame_to(int type, const uint8_t *payload, size_t n, int total_blocks, int n_qtables, int8_t *mv, uint8_t *has, Sink &sink, uint8_t qidx[3])
+{
+    return type == 2 ? parse_pframe_to(payload, n, total_blocks, n_qtables, mv, has, sink, qidx) : parse_iframe_to(payload, n, total_blocks, n_qtables, sink, qidx);
 }
 inline int parse_iframe(const uint8_t *payload, size_t n, int total_blocks, int n_qtables, int16_t *coef, uint8_t qidx[3])
 {

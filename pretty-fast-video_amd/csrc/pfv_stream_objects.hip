@@ -39,6 +39,21 @@ struct PinnedBuf {
     size_t size() const { return n; }
     void swap(PinnedBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(pinned, o.pinned); }
 };
+// Room for `need` elements in a grow-only device buffer: a new one is made need / grow_div larger than asked.  `busy`: the stream to wait for
+// before the old buffer is freed; nullptr when the caller knows that nothing on the device uses it any more.
+template <class T>
+static int dev_room(pfv_ctx *ctx, T **p, size_t *cap, size_t need, size_t grow_div, const hipStream_t *busy = nullptr)
+{
+    if (need <= *cap) return PFV_OK;
+    if (*p) {
+        if (busy) HIP_TRY(ctx, hipStreamSynchronize(*busy));
+        (void)hipFree(*p); *p = nullptr; *cap = 0;
+    }
+    need += need / grow_div;
+    HIP_TRY(ctx, hipMalloc((void **)p, need * sizeof(T)));
+    *cap = need;
+    return PFV_OK;
+}
 
 struct pfv_encoder {
     pfv_ctx *ctx = nullptr;
@@ -73,6 +88,7 @@ struct pfv_encoder {
 // the q indices.  A p-frame's block headers are read on the device since round 5 (k_hdr_*: motion vectors, has_coeff, the first bit of the run
 // streams), the list of coded macroblocks is made there from the has_coeff bytes (k_entd_coded).
 // The payload is copied to `bytes_dst` (page-locked staging, >= plen + 16 bytes).  The caller has set k.byte_off / k.frame_off.
+// A packet the host has to read (rc or host_parse) is left with n_sub = hdr_wgs = 0: it gets no workgroup in its window (entd_number).
 // header workgroups (k_hdr_*) of a p-frame packet: 2 048 bits each, as many as its headers can take (16 bits per macroblock) or its payload has
 static inline uint32_t entd_hdr_wgs(size_t tb, size_t plen)
 {
@@ -183,7 +199,7 @@ static int parse_to_lists(const uint8_t *payload, size_t plen, int type, size_t 
                           size_t *n_out, uint8_t qidx[3])
 {
     ListSink sink{ent, cap, counts, tb};
-    const int rc = type == 2 ? parse_pframe_to(payload, plen, (int)tb, n_qtables, mv, has, sink, qidx) : parse_iframe_to(payload, plen, (int)tb, n_qtables, sink, qidx);
+    const int rc = parse_frame_to(type, payload, plen, (int)tb, n_qtables, mv, has, sink, qidx);
     sink.finish();
     *n_out = sink.n;
     return rc;
@@ -222,6 +238,26 @@ static void entd_launch(hipStream_t stream, const EdBufs &b, unsigned np, unsign
     hipLaunchKernelGGL(k_entd_emit, dim3(ng), dim3(kEdThreads), 0, stream, b);
 }
 
+// Numbers the packets [pa, pb) of a window -- their first subsequence, workgroup and header workgroup among all of the descriptor array's, counted
+// on in `n` -- and lists their workgroups (packet, which kEdOwn subsequences of it) in `groups` from n.groups on.  Returns the most header
+// workgroups any of them has.
+struct EntdTotals { size_t sub = 0, groups = 0, hdr = 0; };
+static unsigned entd_number(EdPacket *pk, size_t pa, size_t pb, uint2 *groups, EntdTotals &n)
+{
+    unsigned max_hdr = 0;
+    for (size_t j = pa; j < pb; j++) {
+        EdPacket &k = pk[j];
+        k.sub_first = (uint32_t)n.sub;
+        k.grp_first = (uint32_t)n.groups;
+        k.hdr_first = (uint32_t)n.hdr;
+        n.sub += k.n_sub;
+        n.hdr += k.hdr_wgs;
+        max_hdr = std::max(max_hdr, (unsigned)k.hdr_wgs);
+        for (uint32_t blk = 0; blk * (uint32_t)kEdOwn < k.n_sub; blk++) groups[n.groups++] = make_uint2((unsigned)j, blk);
+    }
+    return max_hdr;
+}
+
 struct DecEvent {
     enum Kind { FRAME, DROP, END, ERROR } kind = END;
     enum State { FREE, QUEUED, RUNNING, DONE } state = FREE;
@@ -243,7 +279,7 @@ struct DecEvent {
     bool dev_form = false, host_parse = false;
     PinnedBuf<uint8_t> bytes;            // the payload (+ 16)
     PinnedBuf<EdPacket> pk;              // 1
-    PinnedBuf<uint2> groups;             // workgroups of the packet
+    PinnedBuf<uint2> groups;             // workgroups of the packet (entd_window_enqueue)
 };
 
 // switches, shape and counters of the device entropy stage in pfv_decoder / pfv_batch_decoder (the buffers: DecWindow)
@@ -257,6 +293,13 @@ struct DecEntd {
     long packets_dev = 0, packets_host = 0;
 };
 constexpr uint32_t kDecEntdMinBytes = 64 * 1024;   // below this the launches cost more than the host parser needs for the packet
+// the stage's options as the context has them now (PFV_OPT_ENTROPY_DECODE, PFV_OPT_ENTDEC_*); false: the host parser reads every packet
+static bool entd_take_options(const pfv_ctx *ctx, bool *force, uint32_t *sub_bits, int *launches, int *inner)
+{
+    *force = ctx->opt_entropy_decode == PFV_ENTROPY_DECODE_DEVICE;
+    *sub_bits = (uint32_t)ctx->opt_entdec_lane_bits; *launches = ctx->opt_entdec_launches; *inner = ctx->opt_entdec_inner;
+    return ctx->opt_entropy_decode != PFV_ENTROPY_DECODE_HOST;
+}
 
 // device side of one packet's window in pfv_decoder.  Two alternate: the window of the NEXT packet (uploads, k_entd_*, status) runs on a
 // second stream under the decode launch and the frame download of the current one.
@@ -275,7 +318,13 @@ struct DecWindow {
     uint8_t *has_dev = nullptr;
     PinnedBuf<uint32_t> status_host;
     hipEvent_t done = nullptr;
-    DecEvent *owner = nullptr;           // the packet whose window is enqueued / was decoded from this set
+    const void *owner = nullptr;         // an identity only: the packet (pfv_decoder) or staging set (pfv_batch_decoder) whose window is enqueued on this set
+    EdBufs bufs() const                  // the kernels' view of the set: packets and workgroups count from 0
+    {
+        const size_t ts = sub_cap / 4;
+        return EdBufs{bytes_dev, pk_dev, groups_dev, sub_dev, sub_dev + ts, sub_dev + 2 * ts, wgsum_dev, coded_dev, lists.ptr_dev, lists.counts_dev, status_dev, 0u, 0u,
+                      hdr_maps_dev, hdr_start_dev, mv_dev, has_dev};
+    }
     void destroy()
     {
         for (void *p : {(void *)bytes_dev, (void *)pk_dev, (void *)status_dev, (void *)coded_dev, (void *)groups_dev, (void *)sub_dev, (void *)wgsum_dev, (void *)mv_dev, (void *)has_dev,
@@ -324,6 +373,65 @@ struct ListStage {
     }
 };
 
+// One window of the stage on set w, all on `st`: the S packets entd_prepare left in `pk` (payloads of `plen` bytes copied to `bytes` at their
+// byte_off, `bytes_total` in all) are numbered, go up with their workgroup list, k_hdr_* / k_entd_* read them into the set's lists, the
+// statuses come down and w.done is recorded.  S and the macroblock count are the set's (entd_windows_make).  The set is idle: its last window
+// was consumed and decoded.
+static int entd_window_enqueue(pfv_ctx *ctx, const DecEntd &v, DecWindow &w, hipStream_t st, EdPacket *pk, const uint8_t *bytes, size_t bytes_total, const size_t *plen,
+                               PinnedBuf<uint2> &groups, const void *owner)
+{
+    const size_t S = w.lists.frames, tb = w.lists.tb;
+    size_t n_groups = 0;
+    for (size_t k = 0; k < S; k++) n_groups += (pk[k].n_sub + kEdOwn - 1) / kEdOwn;
+    if (!groups.resize(n_groups + 1)) return fail(ctx, PFV_ERR_NOMEM, "pinned staging");
+    EntdTotals n;
+    const unsigned max_hdr = entd_number(pk, 0, S, groups.data(), n);
+    if (n.sub >= 0xffffffffull) return fail(ctx, PFV_ERR_NOMEM, "device entropy stage: payloads too large for one window");
+    int rc;
+    if ((rc = dev_room(ctx, &w.bytes_dev, &w.bytes_cap, bytes_total + 64, 2))) return rc;
+    if ((rc = dev_room(ctx, &w.groups_dev, &w.groups_cap, n_groups + 1, 2))) return rc;
+    if ((rc = dev_room(ctx, &w.sub_dev, &w.sub_cap, (n.sub + 1) * 4, 2))) return rc;
+    if ((rc = dev_room(ctx, &w.wgsum_dev, &w.wgsum_cap, n_groups + 1, 2))) return rc;
+    if ((rc = dev_room(ctx, &w.hdr_maps_dev, &w.hdr_maps_cap, (n.hdr + 1) * 8, 2))) return rc;
+    if ((rc = dev_room(ctx, &w.hdr_start_dev, &w.hdr_start_cap, n.hdr + 1, 2))) return rc;
+    // every packet's list: its place in the window's pool from the packet's size
+    size_t total = 0;
+    w.list_room.assign(S, 0);
+    for (size_t k = 0; k < S; k++) { w.list_room[k] = entd_pool_cap(tb, plen[k]); total += w.list_room[k]; }
+    w.lists.drop_spill();
+    if ((rc = w.lists.room(ctx, total))) return rc;
+    total = 0;
+    for (size_t k = 0; k < S; k++) { w.lists.ptr_host.data()[k] = w.lists.ent + total; total += w.list_room[k]; }
+    HIP_TRY(ctx, hipMemcpyAsync(w.lists.ptr_dev, w.lists.ptr_host.data(), S * sizeof(uint32_t *), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(w.bytes_dev, bytes, bytes_total, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(w.pk_dev, pk, S * sizeof(EdPacket), hipMemcpyHostToDevice, st));
+    if (n_groups) HIP_TRY(ctx, hipMemcpyAsync(w.groups_dev, groups.data(), n_groups * sizeof(uint2), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(w.status_dev, 0, S * sizeof(uint32_t), st));
+    if (n_groups) {
+        entd_launch(st, w.bufs(), (unsigned)S, (unsigned)n_groups, max_hdr, v.launches, v.inner);
+        if ((rc = launch_check(ctx, "k_entd_*"))) return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(w.status_host.data(), w.status_dev, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipEventRecord(w.done, st));
+    w.owner = owner;
+    return PFV_OK;
+}
+// Packet k of window w is for the host parser (the device stage was not certain about it, or could not take it): the parser reads it into `hp`
+// and decides; its list goes up into the packet's place on `stream`, a p-frame's block headers with it (the device's read of them is not what
+// is decoded).  `hp` is free again when `stream` has passed this point.  Returns the parser's status, or that of a failed upload.
+static int entd_host_parse(pfv_ctx *ctx, ListStage &hp, DecWindow &w, size_t k, const uint8_t *payload, size_t plen, int type, int n_qtables, int8_t *mv, uint8_t *has, uint8_t qidx[3],
+                           hipStream_t stream)
+{
+    const size_t tb = w.lists.tb;
+    const int prc = hp.parse(payload, plen, type, tb, n_qtables, mv, has, w.list_room[k], qidx);
+    if (prc) return fail(ctx, prc, prc == PFV_ERR_NOMEM ? "pinned list staging" : "malformed packet payload");
+    const int rc = upload_lists(ctx, w.lists, k, w.list_room[k], hp.ent.data(), hp.n, hp.counts.data(), stream);
+    if (rc || type != 2) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(w.mv_dev + k * tb * 2, mv, tb * 2, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w.has_dev + k * tb, has, tb, hipMemcpyHostToDevice, stream));
+    return PFV_OK;
+}
+
 constexpr int kDecWindows = 4;           // pfv_decoder: windows in flight -- the packet being decoded and up to three behind it
 struct pfv_decoder {
     DecEntd entd;                        // switches, shape and counters of the device entropy stage (its buffers: win[])
@@ -350,15 +458,6 @@ struct pfv_decoder {
     bool quit = false;
 };
 
-static void put_u16(std::vector<uint8_t> &o, unsigned v) { o.push_back((uint8_t)v); o.push_back((uint8_t)(v >> 8)); }
-static void put_u32(std::vector<uint8_t> &o, uint32_t v) { for (int i = 0; i < 4; i++) o.push_back((uint8_t)(v >> (8 * i))); }
-static void put_packet(std::vector<uint8_t> &o, uint8_t type, const std::vector<uint8_t> *payload)
-{
-    o.push_back(type);
-    put_u32(o, payload ? (uint32_t)payload->size() : 0u);
-    if (payload) o.insert(o.end(), payload->begin(), payload->end());
-}
-
 extern "C" {
 
 // Encoder::new (src/enc.rs:37-73): q-tables from quality, prev_frame = new_padded, write_header (:190-219) -- for a ladder of qualities: the
@@ -378,17 +477,7 @@ PFV_API int pfv_encoder_create_ladder(pfv_ctx *ctx, int width, int height, int f
         pfv_encoder_destroy(e);
         return fail(ctx, PFV_ERR_NOMEM, "pfv_encoder_create: pinned staging");
     }
-    static const char magic[8] = {'P', 'F', 'V', 'I', 'D', 'E', 'O', 0};      // common.rs:1
-    e->out.insert(e->out.end(), magic, magic + 8);
-    put_u32(e->out, 211);                                                      // common.rs:2
-    put_u16(e->out, (unsigned)width); put_u16(e->out, (unsigned)height); put_u16(e->out, (unsigned)framerate);
-    put_u16(e->out, 4u * (unsigned)n_rungs);
-    for (int r = 0; r < n_rungs; r++) {
-        int32_t q[4][64];
-        pfv_qtables_from_quality(qualities[r], q[0], q[1], q[2], q[3], nullptr);
-        for (int t = 0; t < 4; t++)                                            // intra_l, intra_c, inter_l, inter_c
-            for (int i = 0; i < 64; i++) put_u16(e->out, (unsigned)q[t][i]);
-    }
+    put_header(e->out, width, height, framerate, qualities, n_rungs);
     *out = e;
     return PFV_OK;
 }
@@ -494,9 +583,7 @@ static int encode_on_device(pfv_encoder *e, bool pframe)
     if (!e->payload.resize(std::max<size_t>(nbytes, 1 << 20))) return fail(ctx, PFV_ERR_NOMEM, "pinned payload staging");
     if ((rc = pfv_enc_payload_fetch(s, 0, e->payload.data(), nbytes))) return rc;
     e->poisoned = false;
-    e->out.push_back(pframe ? 2 : 1);
-    put_u32(e->out, nbytes);
-    e->out.insert(e->out.end(), e->payload.data(), e->payload.data() + nbytes);
+    put_packet(e->out, pframe ? 2 : 1, e->payload.data(), nbytes);
     fill_report(e, pframe ? 2 : 1, 5 + (size_t)nbytes);
     rate_frame_written(e, pframe, nbytes);
     return PFV_OK;
@@ -548,7 +635,7 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung), (uint8_t)(4 * e->hot->rung + 1), (uint8_t)(4 * e->hot->rung + 1)};
     if (!serialize_iframe(payload, e->coef.data(), e->total_blocks, qidx))
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
-    put_packet(e->out, 1, &payload);
+    put_packet(e->out, 1, payload.data(), payload.size());
     e->poisoned = false;
     fill_report(e, 1, 5 + payload.size());
     rate_frame_written(e, false, payload.size());
@@ -572,7 +659,7 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
     const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung + 2), (uint8_t)(4 * e->hot->rung + 3), (uint8_t)(4 * e->hot->rung + 3)};
     if (!serialize_pframe(payload, e->mv.data(), e->has.data(), e->coef.data(), e->total_blocks, qidx))
         return fail(e->ctx, PFV_ERR_FORMAT, "coefficient needs more than 15 size bits (src/rle.rs:44)");
-    put_packet(e->out, 2, &payload);
+    put_packet(e->out, 2, payload.data(), payload.size());
     e->poisoned = false;
     fill_report(e, 2, 5 + payload.size());
     rate_frame_written(e, true, payload.size());
@@ -584,7 +671,7 @@ PFV_API int pfv_encoder_encode_dropframe(pfv_encoder *e)
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:176)");
-    put_packet(e->out, 1, nullptr);
+    put_packet(e->out, 1, nullptr, 0);
     fill_report(e, 3, 5);
     return PFV_OK;
 }
@@ -594,7 +681,7 @@ PFV_API int pfv_encoder_finish(pfv_encoder *e)
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:183)");
     e->finished = true;
-    put_packet(e->out, 0, nullptr);
+    put_packet(e->out, 0, nullptr, 0);
     return PFV_OK;
 }
 PFV_API int pfv_encoder_bytes(pfv_encoder *e, const uint8_t **data, size_t *len)

@@ -365,6 +365,100 @@ def check_empty_pframe_packet(pkg, ctx, oracle, w=48, h=32):
     bd.close()
 
 
+def _packet_starts(data, hdr):
+    """positions of the packet heads of an intact stream, the EOF marker's included"""
+    pos, starts = hdr, []
+    while pos + 5 <= len(data):
+        starts.append(pos)
+        if data[pos] == 0:
+            break
+        pos += 5 + int.from_bytes(data[pos + 1:pos + 5], "little")
+    return starts
+
+
+def check_open_errors_all_decoders(pkg, ctx, oracle, w=48, h=32):
+    """Damaged and truncated HEADERS through every decoder object: 44 lengths of one clip x 5 variants (intact, wrong magic, wrong version, five
+    q-tables announced, none announced).  Each object answers with the oracle's open error (the reference reads magic, version, geometry in
+    that order, src/dec.rs:38-134: a short stream with a wrong version is a VersionError, not an I/O error); where the oracle opens, the
+    object opens and reports the header's geometry and frame rate."""
+    data, _ = encode_clip(pkg, ctx, oracle, w, h, 30, 5, n_frames=4, gop=2)
+    hdr = 20 + 4 * 128
+    lengths = list(range(25)) + list(range(37, hdr, 37)) + [hdr - 1, hdr, hdr + 4, hdr + 5, len(data)]
+    assert len(lengths) == len(set(lengths)) == 44 and len(data) > 20 + 5 * 128
+
+    def variants(cut):
+        yield "intact", cut
+        for name, at, val in (("magic", 0, ord("Q")), ("version", 8, 210), ("five tables", 18, 5), ("no tables", 18, 0)):
+            bad = bytearray(cut)
+            if len(bad) > at:
+                bad[at] = val
+            if at == 18 and len(bad) > 19:
+                bad[19] = 0
+            yield name, bytes(bad)
+    decoders = (("Decoder", lambda x: pkg.Decoder(x, ctx)),
+                ("GopDecoder", lambda x: pkg.GopDecoder(x, ctx, max_gops=2, max_gop_frames=2, threads=0)),
+                ("BatchDecoder, one stream", lambda x: pkg.BatchDecoder([x], ctx)),
+                ("BatchDecoder, two streams", lambda x: pkg.BatchDecoder([x, x], ctx)))
+    L = pkg._lib
+    tally = {L.PFV_ERR_IO: 0, L.PFV_ERR_FORMAT: 0, L.PFV_ERR_VERSION: 0, 0: 0}
+    for n in lengths:
+        for vname, x in variants(data[:n]):
+            odec = OracleStreamDecoder(oracle, x)
+            want = ("open", odec.width, odec.height, odec.framerate) if odec.h else ("open-err", odec.err)
+            tally[0 if odec.h else odec.err] += 1
+            for dname, make in decoders:
+                try:
+                    dec = make(x)
+                except pkg.PfvError as e:
+                    got = ("open-err", e.code)
+                else:
+                    geom = (dec.width, dec.height, dec.framerate)
+                    got = ("open",) + tuple(g() if callable(g) else g for g in geom)
+                    dec.close()
+                assert got == want, f"{dname}, {n} bytes, {vname}: {got}, the oracle {want}"
+    assert sum(tally.values()) == 220 and all(tally.values()), tally      # every outcome class occurs
+    return tally
+
+
+def check_batch_decoder_truncated(pkg, ctx, oracle, w=48, h=32):
+    """BatchDecoder over two copies of a stream that ends early -- at every packet start, inside the packet head (+3), behind it (+5), inside
+    the payload (+9), inside and behind the EOF marker -- with the run streams read by the host pool and by the device stage: the frames
+    before the end are the oracle decoder's, and the stream ends as the oracle's does (end of stream, or the same error code).  At the end of an
+    intact stream advance_frames() returns False where the oracle's last call returns 0 without a frame: the same outcome."""
+    data, _ = encode_clip(pkg, ctx, oracle, w, h, 30, 5, n_frames=4, gop=2)
+    starts = _packet_starts(data, 20 + 4 * 128)
+    assert [data[p] for p in starts] == [1, 2, 1, 2, 0] and starts[-1] == len(data) - 5
+    cuts = sorted({p + d for p in starts for d in (0, 3, 5, 9) if p + d <= len(data)} | {len(data) - 5, len(data) - 1, len(data)})
+    assert len(cuts) == 20, cuts
+    ends = set()
+    for cut in cuts:
+        x = data[:cut]
+        want = _outcomes_oracle(oracle, x)
+        assert want[-1][0] in ("eof", "err")
+        for mode in ("host", "device"):
+            dec = pkg.BatchDecoder([x, x], ctx, entropy=mode)
+            got = []
+            try:
+                for _ in range(64):
+                    try:
+                        fr = dec.advance_frames()
+                    except pkg.PfvError as e:
+                        got.append(("err", e.code))
+                        break
+                    if fr is False:
+                        got += [("none",), ("eof",)]
+                        break
+                    assert fr is None or np.array_equal(fr[0], fr[1])
+                    got.append(("none",) if fr is None else ("frame", fr[0].tobytes()))
+            finally:
+                dec.close()
+            assert [g[0] for g in got] == [x_[0] for x_ in want] and got == want, \
+                f"cut at {cut} of {len(data)}, payloads read on the {mode}: {[g[:1] if g[0] != 'err' else g for g in got]}, the oracle {[g[:1] if g[0] != 'err' else g for g in want]}"
+        ends.add(want[-1])
+    assert ("eof",) in ends and any(e[0] == "err" for e in ends), ends
+    return len(cuts)
+
+
 # ---------------------------------------------------------------------------------------------------------------- GOP-batched objects
 # where the GOP-batched decoder read its packet payloads, summed over every decoder _outcomes closed (PFV_OPT_ENTROPY_DECODE)
 ENTROPY_COUNTS = {"packets_read_on_device": 0, "packets_left_to_host_parser": 0}

@@ -115,6 +115,15 @@ def test_emu_empty_pframe_packet_is_an_error(pkg, emu_ctx, oracle):
     sc.check_empty_pframe_packet(pkg, emu_ctx, oracle)
 
 
+def test_emu_open_errors_all_decoders(pkg, emu_ctx, oracle):
+    """damaged headers: every decoder object answers as the oracle's Decoder::new"""
+    assert all(sc.check_open_errors_all_decoders(pkg, emu_ctx, oracle).values())
+
+
+def test_emu_batch_decoder_truncated(pkg, emu_ctx, oracle):
+    assert sc.check_batch_decoder_truncated(pkg, emu_ctx, oracle) == 20
+
+
 def test_emu_encoder_keeps_nothing(pkg, emu_ctx):
     sc.check_encoder_keeps_nothing(pkg, emu_ctx)
 
