@@ -202,14 +202,7 @@ PFV_API int pfv_batch_encoder_take(pfv_batch_encoder *b, int stream, const uint8
 // packets of a step are bit-parsed (src/dec.rs:226-296, 328-417) on a worker pool, one task per stream, into (index, value)
 // lists in page-locked memory; ONE segmented scatter kernel reads the lists straight from host memory, ONE decode launch
 // serves all streams, ONE copy brings the frames back.  The parse of step t+1 runs while the device works on step t.
-struct BdSet {   // host staging of one step (two sets alternate)
-    PinnedBuf<uint32_t> idx;
-    PinnedBuf<int16_t> val;
-    PinnedBuf<uint32_t> counts;
-    PinnedBuf<int8_t> mv;
-    PinnedBuf<uint8_t> has;
-    std::vector<int> rc;               // per stream: 0, kSinkFull, PFV_ERR_*
-    std::vector<uint8_t> qidx;         // per stream x 3
+struct BdSet : StepStage {   // host staging of one step (two sets alternate): a slot per stream
     std::vector<const uint8_t *> payload;
     std::vector<size_t> len;
     int type = 0;                      // 0 EOF, 1 i-frames, 2 p-frames, 3 drop frames; negative: error found by the scanner
@@ -259,12 +252,7 @@ static void bd_parse_one(pfv_batch_decoder *b, BdSet *s, int k)
         s->counts.data()[k] = 0;
         return;
     }
-    SparseSink sink{s->idx.data() + (size_t)k * b->cap, s->val.data() + (size_t)k * b->cap, b->cap};
-    sink.offset = (size_t)k * tb * 256;
-    uint8_t *q = &s->qidx[(size_t)k * 3];
-    int rc = parse_frame_to(s->type, s->payload[(size_t)k], s->len[(size_t)k], (int)tb, b->n_qtables, s->mv.data() + (size_t)k * tb * 2, s->has.data() + (size_t)k * tb, sink, q);
-    s->counts.data()[k] = (uint32_t)sink.n;
-    s->rc[(size_t)k] = rc;
+    s->parse(k, s->type, s->payload[(size_t)k], s->len[(size_t)k], tb, b->n_qtables, b->cap);
 }
 static void bd_worker(pfv_batch_decoder *b)
 {
@@ -406,8 +394,8 @@ PFV_API int pfv_batch_decoder_create(pfv_ctx *ctx, const uint8_t *const *streams
     const size_t S = (size_t)n_streams, tb = b->total_blocks;
     bool ok = true;
     for (auto &s : b->set) {
-        ok = ok && s.idx.resize(S * b->cap) && s.val.resize(S * b->cap) && s.counts.resize(S) && s.mv.resize(S * tb * 2) && s.has.resize(S * tb);
-        s.rc.assign(S, 0); s.qidx.assign(S * 3, 0); s.payload.assign(S, nullptr); s.len.assign(S, 0);
+        ok = s.make(S, b->cap, tb) && ok;
+        s.payload.assign(S, nullptr); s.len.assign(S, 0);
     }
     ok = ok && b->frames[0].resize(S * b->frame_bytes) && b->frames[1].resize(S * b->frame_bytes);
     DecEntd &v = b->entd;
@@ -517,7 +505,7 @@ PFV_API int pfv_batch_decoder_advance(pfv_batch_decoder *b, const uint8_t **fram
         *frames_out = b->frames[slot].data();
         return 1;
     } else {
-    const bool lists_on_device_bus = s->idx.pinned && s->val.pinned && s->counts.pinned;   // page-locked: the kernel can read them
+    const bool lists_on_device_bus = s->lists_pinned();   // page-locked: the kernel can read them
     if (!dense && !lists_on_device_bus) {   // pageable staging (locked-memory limit): expand the lists on the host instead
         if (!b->dense.resize(total)) return fail(ctx, PFV_ERR_NOMEM, "dense staging");
         memset(b->dense.data(), 0, total * 2);
@@ -535,11 +523,8 @@ PFV_API int pfv_batch_decoder_advance(pfv_batch_decoder *b, const uint8_t **fram
         }
         if (rc) { b->eof = true; return fail(ctx, rc, "malformed packet payload"); }
         HIP_TRY(ctx, hipMemcpyAsync(hot->st_coef, b->dense.data(), total * 2, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        HIP_TRY(ctx, hipMemsetAsync(hot->st_coef, 0, total * 2, ctx->stream));
-        hipLaunchKernelGGL(k_scatter_coef_seg, dim3(64, (unsigned)S), dim3(kThreads), 0, ctx->stream, s->idx.data(), s->val.data(),
-                           s->counts.data(), (uint32_t)b->cap, (uint32_t)total, hot->st_coef);
-        if ((rc = launch_check(ctx, "k_scatter_coef_seg"))) return rc;
+    } else if ((rc = s->scatter(ctx, hot, S, tb, b->cap))) {
+        return rc;
     }
     }
     if (s->type == 2) {

@@ -234,7 +234,8 @@ int pfv_selfcheck_huffman(pfv_ctx *ctx, const int32_t *hists, int n, int on_devi
     return PFV_OK;
 }
 
-#include "pfv_gop.hip"    // GOP-batched stream objects (pfv_gop_encoder, pfv_gop_decoder)
+#include "pfv_gop.hip"    // GOP-batched stream objects: what both use, pfv_gop_encoder
+#include "pfv_gop_decoder.hip"   // ... and pfv_gop_decoder
 
 #include "pfv_comm.hip"   // multi-GPU control plane on RCCL (pfv_comm_*)
 

@@ -372,6 +372,42 @@ struct ListStage {
         return parse_to_lists(payload, plen, type, tb, n_qtables, mv, has, ent.data(), tb * 256, counts.data(), &n, qidx);
     }
 };
+// host staging of one frame step of S slots whose packets the HOST parser reads (pfv_batch_decoder, pfv_gop_decoder): per slot an (index,
+// value) list of `cap` entries with flat indices into [slot][macroblock][256], the block headers, the parse status and the q indices.  One
+// segmented scatter kernel reads the lists where the parsers wrote them (page-locked memory).
+struct StepStage {
+    PinnedBuf<uint32_t> idx;
+    PinnedBuf<int16_t> val;
+    PinnedBuf<uint32_t> counts;
+    PinnedBuf<int8_t> mv;
+    PinnedBuf<uint8_t> has;
+    std::vector<int> rc;               // per slot: 0, kSinkFull (the list overflowed: dense fallback), PFV_ERR_*
+    std::vector<uint8_t> qidx;         // per slot x 3
+    bool make(size_t S, size_t cap, size_t tb)
+    {
+        rc.assign(S, 0); qidx.assign(S * 3, 0);
+        return idx.resize(S * cap) && val.resize(S * cap) && counts.resize(S) && mv.resize(S * tb * 2) && has.resize(S * tb);
+    }
+    bool lists_pinned() const { return idx.pinned && val.pinned && counts.pinned; }   // the scatter kernel can read them
+    // slot k's packet.  Only a packet that parsed leaves a count: a list that overflowed or broke off is never scattered -- pfv_gop_decoder
+    // does not launch such a slot (or uploads its dense form over it), pfv_batch_decoder scatters no step that has one.
+    void parse(int k, int type, const uint8_t *payload, size_t len, size_t tb, int n_qtables, size_t cap)
+    {
+        SparseSink sink{idx.data() + (size_t)k * cap, val.data() + (size_t)k * cap, cap};
+        sink.offset = (size_t)k * tb * 256;
+        rc[(size_t)k] = parse_frame_to(type, payload, len, (int)tb, n_qtables, mv.data() + (size_t)k * tb * 2, has.data() + (size_t)k * tb, sink, &qidx[(size_t)k * 3]);
+        counts.data()[k] = rc[(size_t)k] == 0 ? (uint32_t)sink.n : 0u;
+    }
+    // the lists of slots [0, S) into the session's cleared coefficient staging, on the context's stream
+    int scatter(pfv_ctx *ctx, pfv_dec_session *hot, size_t S, size_t tb, size_t cap)
+    {
+        const size_t total = tb * S * 256;
+        HIP_TRY(ctx, hipMemsetAsync(hot->st_coef, 0, total * 2, ctx->stream));
+        hipLaunchKernelGGL(k_scatter_coef_seg, dim3(64, (unsigned)S), dim3(kThreads), 0, ctx->stream, idx.data(), val.data(), counts.data(), (uint32_t)cap, (uint32_t)total,
+                           hot->st_coef);
+        return launch_check(ctx, "k_scatter_coef_seg");
+    }
+};
 
 // One window of the stage on set w, all on `st`: the S packets entd_prepare left in `pk` (payloads of `plen` bytes copied to `bytes` at their
 // byte_off, `bytes_total` in all) are numbered, go up with their workgroup list, k_hdr_* / k_entd_* read them into the set's lists, the

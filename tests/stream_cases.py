@@ -7,7 +7,8 @@ import os
 
 import numpy as np
 
-from oracle_bind import OracleStreamDecoder, OracleStreamEncoder
+from oracle_bind import OracleEncoder, OracleStreamDecoder, OracleStreamEncoder
+from pfv_stream_builder import ENCODER_QIDX, StreamBuilder
 
 
 def frame_of(pkg, w, h, packed):
@@ -787,6 +788,53 @@ def check_gop_decoder_dense_iframe_failure(pkg, ctx, oracle, w=124, h=212, quali
                 assert got == want, (frac, shape, mode, [x[0] for x in got], [x == y for x, y in zip(got, want)])
     assert hit >= 1 or not require_hit, "no flip produced the failing i-frame this case is about"
     return hit
+
+
+def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, pattern="IPPIPP", bad_at=(1, 2, 4), shapes=((2, 3), (1, 2), (3, 15))):
+    """PFV_ERR_BAD_MV through pfv_gop_decoder: streams written from parts (the oracle encoder's coefficients and headers on the pan content)
+    in which ONE p-frame has the vector of macroblock 0 set to (-1, 0) -- outside the reference plane (src/common.rs:258-259); the kernels
+    flag it and do not follow it.  For every place of the bad packet, batch shape, entropy path and pool size the GOP-batched decoder
+    delivers on every call what the sequential Decoder delivers, the frames behind the error included; both agree with the oracle's decoder
+    up to the error; and the error is PFV_ERR_BAD_MV on the bad packet's call and on no other."""
+    tb = int(pkg._lib.load().pfv_total_blocks(w, h))
+    tabs = pkg.qtables_from_quality(quality)
+    tables = np.stack([np.asarray(tabs[k], np.int64).reshape(64) for k in range(4)])
+    enc = OracleEncoder(oracle, w, h, quality)
+    st = pkg.SyntheticStream(w, h)
+    content = []
+    for t, c in enumerate(pattern):
+        content.append((enc.encode_iframe(st.frame(t)), None, None) if c == "I" else enc.encode_pframe(st.frame(t))[::-1])   # (coef, has, mv)
+    bad_mv = pkg._lib.PFV_ERR_BAD_MV
+    runs = 0
+    for bad in bad_at:
+        assert pattern[bad] == "P"
+        b = StreamBuilder(oracle, w, h, 30, tables, tb)
+        for k, (coef, has, mv) in enumerate(content):
+            if mv is None:
+                b.iframe(coef, ENCODER_QIDX[1])
+                continue
+            mv = mv.copy()
+            if k == bad:
+                mv[0] = (-1, 0)
+            b.pframe(mv, has, coef, ENCODER_QIDX[2])
+        data = b.bytes()
+        want = _outcomes(lambda: pkg.Decoder(data, ctx, lookahead=0), pkg, n_calls=12, stop_at_error=False)
+        kinds = [x[0] for x in want]
+        assert kinds == ["frame"] * bad + ["err"] + ["frame"] * (len(pattern) - bad - 1) + ["none", "eof"], (bad, kinds)
+        assert want[bad] == ("err", bad_mv), (bad, want[bad])
+        ora = _outcomes_oracle(oracle, data)
+        assert ora == want[:bad + 1], (bad, [x[0] for x in ora], ora[-1][1:] if ora[-1][0] == "err" else None)
+        for max_gops, max_len in shapes:
+            for mode in GOP_ENTROPY_MODES:
+                for threads in (0, 2):
+                    got = _outcomes(lambda: pkg.GopDecoder(data, ctx, max_gops=max_gops, max_gop_frames=max_len, threads=threads, entropy=mode), pkg,
+                                    n_calls=12, stop_at_error=False)
+                    what = (bad, max_gops, max_len, mode, threads)
+                    assert [x[0] for x in got] == kinds, (what, [x[0] for x in got])
+                    assert [k for k, x in enumerate(got) if x[0] == "err"] == [bad] and got[bad] == ("err", bad_mv), (what, got[bad])
+                    assert got == want, (what, [x == y for x, y in zip(got, want)])
+                    runs += 1
+    return runs
 
 
 def check_gop_device_entropy(pkg, ctx, oracle, w, h, quality=5, pattern="IPPPPIPPPP", min_device_share=1.0, expect_unsettled=True, only=None):

@@ -296,6 +296,11 @@ def test_emu_gop_decoder_dense_iframe_failure(pkg, emu_ctx, oracle):
     assert sc.check_gop_decoder_dense_iframe_failure(pkg, emu_ctx, oracle, shapes=((8, 15), (2, 2), (1, 15))) >= 1
 
 
+def test_emu_gop_decoder_bad_vector(pkg, emu_ctx, oracle):
+    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes"""
+    assert sc.check_gop_decoder_bad_vector(pkg, emu_ctx, oracle) == 36
+
+
 def test_emu_soak_iterations(pkg, emu_ctx, oracle, lane_mapping):
     """a few passes of tools/soak.py's randomised iteration (every checker, random geometry / quality / packet pattern / lane mapping /
     option settings) at sizes the emulator finishes in seconds; fixed seeds.  The GPU box runs the same function at full sizes for minutes."""

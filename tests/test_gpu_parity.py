@@ -544,6 +544,11 @@ def test_gop_decoder_dense_iframe_failure(pkg, gpu_ctx, oracle):
     sc.check_gop_decoder_dense_iframe_failure(pkg, gpu_ctx, oracle, 320, 240, 0, require_hit=False)   # another geometry; a flip may leave the packet parseable
 
 
+def test_gop_decoder_bad_vector(pkg, gpu_ctx, oracle):
+    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes"""
+    assert sc.check_gop_decoder_bad_vector(pkg, gpu_ctx, oracle) == 36
+
+
 def test_config4_4k_gop15_stream_vs_oracle(pkg, gpu_ctx, oracle):
     """BASELINE config #4 at its stated geometry and GOP pattern, under the driver's eyes: 3840x2160, 31 frames (i-frames at
     0, 15 and 30 -> two full GOP boundaries, README.md:34-41), quality 5, product Encoder -> .pfv bytes -> product Decoder
