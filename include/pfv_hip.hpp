@@ -160,6 +160,16 @@ class Encoder {
     int n_rungs() const { return pfv_encoder_rungs(h_); }
     // byte budget per p-frame payload, 0 = off (pfv_encoder_set_rate)
     void set_rate(uint32_t pframe_budget) { ctx_.check(pfv_encoder_set_rate(h_, pframe_budget)); }
+    // payload bytes of `f` as an i-frame at every rung (0xffffffff: not encodable there); the stream, the reference and the rung stay as they are
+    std::vector<uint32_t> probe_iframe(const VideoFrame &f) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        ctx_.check(pfv_encoder_probe_iframe(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data()));
+        return sizes;
+    }
+    // byte budget per i-frame payload, 0 = off: encode_iframe takes the finest rung whose probed payload fits, the coarsest if none does
+    void set_iframe_budget(uint32_t iframe_budget) { ctx_.check(pfv_encoder_set_iframe_budget(h_, iframe_budget)); }
     // of the last encode_* call; Error(PFV_ERR_STATE) when reports are off, nothing has been encoded yet or that call failed
     FrameReport last_report() const
     {

@@ -331,8 +331,27 @@ PFV_API int pfv_encoder_rungs(pfv_encoder *e);
  * A p-frame is encoded at the current rung; with n = its payload bytes: n > pframe_budget moves the rung one step coarser, otherwise
  * 2 n <= pframe_budget one step finer, clamped to the ladder -- soft by one frame.  The factor 2 is a design constant (hysteresis wider
  * than the step between neighbouring qualities), not a measurement.  I-frames, drop frames and failed calls leave the rung alone;
- * pfv_encoder_set_rung may still be called and simply sets the state.  (Choosing an i-frame's rung by size needs a size probe; none exists yet.) */
+ * pfv_encoder_set_rung may still be called and simply sets the state.  An i-frame's rung is chosen by size with pfv_encoder_set_iframe_budget
+ * (below): the rung it picks is where this rule goes on from. */
 PFV_API int pfv_encoder_set_rate(pfv_encoder *e, uint32_t pframe_budget);
+
+/* ------------------------------------------------------------------ i-frame size probe, i-frame byte budget  [B]
+ * payload bytes (the packet adds 5) that pfv_enc_iframe_dev + the entropy stage would produce for these frames at EVERY rung of the
+ * session, from one read of the frames.  Reads no session state but the tables, window and frame stride; changes none: prev_frame, the
+ * ping-pong index and the current rung stay as they are.  sizes_dev: uint32[n_streams][n_rungs], entries of slots outside the window left
+ * alone; 0xffffffff = not encodable at that rung.  stats_dev (may be NULL): uint32[n_streams][n_rungs][17], the 16 symbol counts and the
+ * sum of coefficient sizes (undefined where the size is 0xffffffff).  Asynchronous on the context's stream; recordable in a graph (scratch
+ * rule as pfv_frames_sse_dev: the session's accumulator is allocated by the first call, so call once before pfv_graph_begin).  Two launches,
+ * k_probe_iframe + k_probe_sizes (csrc/pfv_probe_kernels.hip); no host-side clear, no host synchronisation. */
+PFV_API int pfv_enc_probe_iframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev);
+PFV_API int pfv_enc_probe_iframe(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out);      /* host buffers, all slots, packed; synchronises */
+PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/);
+/* I-frame byte budget in payload bytes, 0 = off (default: today's behaviour, byte for byte).  On: encode_iframe probes the frame first and
+ * encodes it at the FINEST rung whose payload fits the budget, or the coarsest rung if none does (a scan from rung 0 -- sizes need not be
+ * monotone); that rung becomes the current rung, so the p-frames behind it and pfv_encoder_set_rate's rule start from it.  Costs one extra
+ * launch pair and one 4 * n_rungs-byte download (with its synchronisation) per i-frame, on both entropy paths; the frame goes up once.  A
+ * one-rung encoder has nothing to choose and does not probe. */
+PFV_API int pfv_encoder_set_iframe_budget(pfv_encoder *e, uint32_t iframe_budget);
 
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);

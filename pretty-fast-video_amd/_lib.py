@@ -166,6 +166,10 @@ SIGNATURES = [
     ("pfv_encoder_rung", c_int, [_P]),
     ("pfv_encoder_rungs", c_int, [_P]),
     ("pfv_encoder_set_rate", c_int, [_P, ctypes.c_uint32]),
+    ("pfv_enc_probe_iframe_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_enc_probe_iframe", c_int, [_P, _P, _P]),
+    ("pfv_encoder_probe_iframe", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_encoder_set_iframe_budget", c_int, [_P, ctypes.c_uint32]),
     ("pfv_batch_encoder_create", c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(_P)]),
     ("pfv_batch_encoder_frames", _P, [_P]),
     ("pfv_batch_encoder_encode", c_int, [_P, c_int, _P]),

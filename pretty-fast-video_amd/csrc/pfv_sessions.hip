@@ -105,6 +105,9 @@ struct pfv_enc_session {
     uint32_t *q_map = nullptr;
     uint64_t *q_sse = nullptr;
     uint64_t *report_host = nullptr;         // pfv_encoder's frame reports are on: [n_streams][3], page-locked, owned by the encoder
+    // i-frame size probe (pfv_probe.hip): the kernels' accumulator [n_streams][n_rungs][kProbeAcc], zero between calls; sizes of the host-buffer form
+    uint32_t *probe_acc = nullptr;
+    uint32_t *probe_sizes = nullptr;
     // device entropy stage (pfv_enc_entropy_enable)
     bool ent_on = false;
     uint32_t ent_cap = 0;
@@ -224,7 +227,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -331,23 +334,29 @@ static int enc_staging(pfv_enc_session *s)
     return PFV_OK;
 }
 
-PFV_API int pfv_enc_iframe(pfv_enc_session *s, const uint8_t *frames, int16_t *coef_out)
+// frames == nullptr: they lie in the session's frame staging already (pfv_encoder's i-frame budget has probed them there)
+static int enc_iframe_host(pfv_enc_session *s, const uint8_t *frames, int16_t *coef_out)
 {
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
     pfv_ctx *ctx = s->ctx;
-    if (!frames || !coef_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_iframe: null buffer");
     if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, "pfv_enc_iframe: the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = enc_staging(s);
     if (rc) return rc;
     size_t n = (size_t)s->geom.mbs_per_frame * s->n_streams;
-    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
-                                hipMemcpyHostToDevice, ctx->stream));
+    if (frames)
+        HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
+                                    hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_iframe_dev(s, s->st_frames, s->st_coef))) return rc;
     if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
+}
+PFV_API int pfv_enc_iframe(pfv_enc_session *s, const uint8_t *frames, int16_t *coef_out)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    if (!frames || !coef_out) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_iframe: null buffer");
+    return enc_iframe_host(s, frames, coef_out);
 }
 
 PFV_API int pfv_enc_pframe(pfv_enc_session *s, const uint8_t *frames, int8_t *mv_out, uint8_t *has_coef_out,

@@ -78,6 +78,7 @@ struct pfv_encoder {
     // quality ladder (pfv_encoder_create_ladder): the current rung is the session's; rate control (pfv_encoder_set_rate)
     int last_rung = -1;                    // rung of the last frame written (-1: none yet)
     uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
+    uint32_t budget_i = 0;                 // i-frame payload bytes (pfv_encoder_set_iframe_budget); 0: off
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -542,6 +543,14 @@ PFV_API int pfv_encoder_set_rate(pfv_encoder *e, uint32_t pframe_budget)
     return PFV_OK;
 }
 
+// i-frame byte budget per payload, 0 = off; the rule is at the declaration (include/pfv_hip_ext.h) and in choose_iframe_rung
+PFV_API int pfv_encoder_set_iframe_budget(pfv_encoder *e, uint32_t iframe_budget)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    e->budget_i = iframe_budget;
+    return PFV_OK;
+}
+
 // the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
 static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
 {
@@ -590,8 +599,23 @@ static void rate_frame_written(pfv_encoder *e, bool pframe, size_t payload_bytes
     else if (2 * (uint64_t)payload_bytes <= e->budget_p) s->rung = std::max(s->rung - 1, 0);
 }
 
-// One frame through the device entropy stage: planes up, kernels, payload size then payload bytes down.
-static int encode_on_device(pfv_encoder *e, bool pframe)
+// the planes into the session's frame staging (which exists), on the context's stream: read until the caller's next synchronisation
+static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+{
+    pfv_enc_session *s = e->hot;
+    pfv_ctx *ctx = e->ctx;
+    const size_t ny = (size_t)e->width * e->height, nc = (size_t)(e->width / 2) * (e->height / 2);
+    const bool packed = u == y + ny && v == u + nc;   // a packed frame: one copy
+    hipError_t he = hipMemcpyAsync(s->st_frames, y, packed ? ny + 2 * nc : ny, hipMemcpyHostToDevice, ctx->stream);
+    if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny, u, nc, hipMemcpyHostToDevice, ctx->stream);
+    if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny + nc, v, nc, hipMemcpyHostToDevice, ctx->stream);
+    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "plane upload"); }
+    return PFV_OK;
+}
+
+// One frame through the device entropy stage: planes up (unless the i-frame budget's probe has put them there: `staged`), kernels, payload size
+// then payload bytes down.
+static int encode_on_device(pfv_encoder *e, bool pframe, bool staged = false)
 {
     pfv_enc_session *s = e->hot;
     pfv_ctx *ctx = e->ctx;
@@ -599,14 +623,8 @@ static int encode_on_device(pfv_encoder *e, bool pframe)
     int rc = enc_staging(s);
     if (!rc) rc = pfv_enc_entropy_enable(s, 0);
     if (rc) return rc;
-    {   // the caller's planes are read until the first synchronisation below (pfv_enc_payload_sizes); every exit before it synchronises too
-        const size_t ny = (size_t)e->width * e->height, nc = (size_t)(e->width / 2) * (e->height / 2);
-        const bool packed = e->plane[1] == e->plane[0] + ny && e->plane[2] == e->plane[1] + nc;   // a packed frame: one copy
-        hipError_t he = hipMemcpyAsync(s->st_frames, e->plane[0], packed ? ny + 2 * nc : ny, hipMemcpyHostToDevice, ctx->stream);
-        if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny, e->plane[1], nc, hipMemcpyHostToDevice, ctx->stream);
-        if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny + nc, e->plane[2], nc, hipMemcpyHostToDevice, ctx->stream);
-        if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "plane upload"); }
-    }
+    // the caller's planes are read until the first synchronisation below (pfv_enc_payload_sizes); every exit before it synchronises too
+    if (!staged && (rc = upload_planes(e, e->plane[0], e->plane[1], e->plane[2]))) return rc;
     rc = pframe ? pfv_enc_pframe_dev(s, s->st_frames, s->st_mv, s->st_has, s->st_coef) : pfv_enc_iframe_dev(s, s->st_frames, s->st_coef);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     // from here on prev_frame has moved to this frame: a failure leaves the encoder's reference ahead of the stream
@@ -656,6 +674,24 @@ PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out)
     return PFV_OK;
 }
 
+// The i-frame byte budget: the frame goes up into the session's staging, the probe sizes it at every rung, and the finest rung whose payload
+// fits becomes the current rung (the coarsest if none does; a rung the probe marks not encodable does not fit).
+static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+{
+    pfv_enc_session *s = e->hot;
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    int rc = enc_staging(s);
+    if (!rc) rc = upload_planes(e, y, u, v);
+    uint32_t sizes[kMaxRungs];
+    if (!rc) rc = probe_staged(s, sizes);
+    if (rc) return rc;
+    int rung = s->n_rungs - 1;
+    for (int r = 0; r < s->n_rungs; r++)
+        if (sizes[r] != kEntErrOversize && sizes[r] <= e->budget_i) { rung = r; break; }
+    s->rung = rung;
+    return PFV_OK;
+}
+
 // Encoder::encode_iframe (src/enc.rs:75-123)
 PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
 {
@@ -663,9 +699,11 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
-    if (e->device_entropy) return encode_on_device(e, false);      // an i-frame replaces prev_frame entirely: clears a poisoned state
+    const bool budget = e->budget_i != 0 && e->hot->n_rungs > 1;   // one rung: nothing to choose
+    if (budget && (rc = choose_iframe_rung(e, y, u, v))) return rc;
+    if (e->device_entropy) return encode_on_device(e, false, budget);      // an i-frame replaces prev_frame entirely: clears a poisoned state
     if ((rc = host_entropy_staging(e))) return rc;
-    if ((rc = pfv_enc_iframe(e->hot, e->frame.data(), e->coef.data()))) return rc;
+    if ((rc = enc_iframe_host(e->hot, budget ? nullptr : e->frame.data(), e->coef.data()))) return rc;
     e->poisoned = true;
     std::vector<uint8_t> payload;
     const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung), (uint8_t)(4 * e->hot->rung + 1), (uint8_t)(4 * e->hot->rung + 1)};
@@ -676,6 +714,17 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     fill_report(e, 1, 5 + payload.size());
     rate_frame_written(e, false, payload.size());
     return PFV_OK;
+}
+// payload bytes of this frame as an i-frame at every rung; the encoder's stream, reference and rung stay as they are
+PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!y || !u || !v || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe: null buffer");
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    int rc = enc_staging(e->hot);
+    if (!rc) rc = upload_planes(e, y, u, v);
+    if (!rc) rc = probe_staged(e->hot, sizes_out);
+    return rc;
 }
 // Encoder::encode_pframe (src/enc.rs:125-173)
 PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)

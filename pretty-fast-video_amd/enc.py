@@ -16,9 +16,10 @@ from .frame import VideoFrame
 
 class Encoder:
     def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
-                 frame_report: bool = False, qualities=None):
+                 frame_report: bool = False, qualities=None, iframe_budget: int = 0):
         """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
-        quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame"""
+        quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame.  ``iframe_budget``: see
+        ``set_iframe_budget``"""
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
         h = ctypes.c_void_p()
@@ -35,6 +36,8 @@ class Encoder:
         # frame_report: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
         if frame_report:
             ctx.check(ctx._lib.pfv_encoder_set_frame_report(h, 1))
+        if iframe_budget:
+            ctx.check(ctx._lib.pfv_encoder_set_iframe_budget(h, int(iframe_budget)))
         self.finished = False
         ctx._sessions.add(self)
         self._flush()                                               # header (src/enc.rs:70)
@@ -88,6 +91,21 @@ class Encoder:
         """byte budget per p-frame payload (0: off): a p-frame over it moves the next frame one rung coarser, one at half the budget or
         less one rung finer (pfv_encoder_set_rate)"""
         self.ctx.check(self.ctx._lib.pfv_encoder_set_rate(self.handle, int(pframe_budget)))
+
+    def set_iframe_budget(self, iframe_budget: int = 0):
+        """byte budget per i-frame payload (0: off): encode_iframe probes the frame and encodes it at the finest rung whose payload fits,
+        the coarsest if none does; that rung becomes the current rung (pfv_encoder_set_iframe_budget)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_iframe_budget(self.handle, int(iframe_budget)))
+
+    def probe_iframe(self, frame: VideoFrame):
+        """payload bytes of `frame` as an i-frame at every rung, uint32 [n_rungs] (0xffffffff: not encodable at that rung); the stream, the
+        encoder's reference and the rung stay as they are"""
+        import numpy as np
+        self._check_frame(frame)
+        sizes = np.zeros(self.n_rungs, dtype=np.uint32)
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
+                                                              ptr(frame.plane_v.pixels), ptr(sizes)))
+        return sizes
 
     @property
     def last_report(self):

@@ -73,6 +73,21 @@ class EncoderSession(_Geometry):
         """the rung of the encode / pack launches that follow (all slots of a launch share it)"""
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_rung(self.handle, int(rung)))
 
+    # i-frame size probe -------------------------------------------------
+    def probe_iframe(self, frames) -> np.ndarray:
+        """payload bytes of every stream's frame as an i-frame at every rung, uint32 [n_streams, n_rungs], from one read of the frames
+        (pfv_enc_probe_iframe); 0xffffffff: not encodable at that rung.  Leaves prev_frame and the rung alone."""
+        f = self._frames(frames)
+        sizes = np.zeros((self.n_streams, self.n_rungs), dtype=np.uint32)
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_iframe(self.handle, ptr(f), ptr(sizes)))
+        return sizes
+
+    def probe_iframe_dev(self, frames_dev: int, sizes_dev: int, stats_dev: int = 0):
+        """asynchronous on the context's stream; sizes_dev uint32 [n_streams][n_rungs], stats_dev uint32 [n_streams][n_rungs][17] or 0.
+        Honours the window and the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_iframe_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
+                                                              ctypes.c_void_p(stats_dev or 0)))
+
     # host-buffer forms ------------------------------------------------
     def _frames(self, frames) -> np.ndarray:
         f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -11,6 +11,14 @@ i-frames and p-frames, and the mean PSNR of Y, U, V and of the whole frame.
 input packed, reconstruction padded, map to scratch -- against pfv_dec_get_frame_dev (k_crop_frames) over the same 96 frames, which
 moves the same bytes; HIP events around every launch, warm-up, median of the samples.  And what the reports cost pfv_encoder per
 frame at 1080p (host clock around calls that end in a synchronise), against the same encoder with reports off.
+
+--probe: the i-frame size probe (pfv_encoder_probe_iframe) on the clip's first frame with --qualities as the ladder -- probed against written
+payload bytes per rung (frame reports) -- and then its timing (on the GPU box): A = the probe's two launches (k_probe_iframe + k_probe_sizes)
+against B = what the tree offered before for the same answer, per rung pfv_enc_iframe_dev + the entropy stage, at 96 x 1080p and 1 x 1080p,
+ladders 0,2,5,7,10 and 0..10.  B twice: with the stage as a caller runs it (all four k_ent_* kernels), and with a payload capacity of 24 bytes,
+where k_ent_init / k_ent_pack leave at once -- the stage "up to the size" (k_ent_scan + k_ent_codes), B's lower bound.  HIP events on the
+context's stream, warm-up, A and B alternating in one process, medians; the whole comparison three times for B's own spread.  Last the
+latency an i-frame budget adds to one pfv_encoder at 1080p (host clock, budget off / on alternating).
 """
 import argparse
 import ctypes
@@ -124,6 +132,102 @@ def time_kernels(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
     return line
 
 
+def probe_sizes_line(pkg, ctx, w, h, kind, ladder):
+    """probed against written payload bytes of the clip's first frame at every rung"""
+    fr = pkg.VideoFrame.from_packed(w, h, pkg.SyntheticStream(w, h, kind=kind).frame(0))
+    enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, frame_report=True, qualities=ladder)
+    probed = [int(v) for v in enc.probe_iframe(fr)]
+    written = []
+    for r in range(len(ladder)):
+        enc.set_rung(r)
+        enc.encode_iframe(fr)
+        written.append(enc.last_report.packet_bytes - 5)
+    enc.close()
+    return {"ladder": ladder, "width": w, "height": h, "kind": kind, "probed_bytes": probed, "written_bytes": written, "equal": probed == written}
+
+
+def time_probe(pkg, ctx, n_streams, ladder, w=1920, h=1080, warmup=3, samples=20, rounds=3):
+    lib = ctx._lib
+    fb, tb, R = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h)), len(ladder)
+    frames, coef, sizes = ctx.alloc(fb * n_streams), ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * R * 4)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, frames)
+    probe = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full.enable_entropy()
+    upto.enable_entropy(payload_cap=24)            # every payload is "over capacity": k_ent_init / k_ent_pack return at once
+    e0, e1 = ctx.event(), ctx.event()
+
+    def trial(enc):
+        for r in range(R):
+            enc.set_rung(r)
+            enc.encode_iframe_dev(frames, coef)
+            enc.pack_iframe_dev(coef)
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got)
+    res = {"probe": [], "trials_full": [], "trials_to_size": []}
+    for _ in range(rounds):
+        res["probe"].append(median_ms(lambda: probe.probe_iframe_dev(frames, sizes)))
+        res["trials_to_size"].append(median_ms(lambda: trial(upto)))
+        res["trials_full"].append(median_ms(lambda: trial(full)))
+    # the answers: the probe's sizes against the trial encodes' (rung by rung, all streams)
+    got = np.zeros((n_streams, R), np.uint32)
+    ctx.download(got, sizes)
+    same = True
+    for r in range(R):
+        full.set_rung(r)
+        full.encode_iframe_dev(frames, coef)
+        full.pack_iframe_dev(coef)
+        same = same and bool(np.array_equal(full.payload_sizes(), got[:, r]))
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    for s in (probe, full, upto):
+        s.close()
+    for p in (frames, coef, sizes):
+        ctx.free(p)
+    a, b, bf = (statistics.median(res[k]) for k in ("probe", "trials_to_size", "trials_full"))
+    spread = max(res["trials_to_size"]) - min(res["trials_to_size"])
+    return {"shape": f"{n_streams} x {w}x{h}", "ladder": ladder, "samples_per_round": samples, "rounds": rounds,
+            "probe_ms": a, "trials_to_size_ms": b, "trials_full_ms": bf, "trials_to_size_spread_ms": spread,
+            "probe_over_trials_to_size": a / b if b else None, "probe_below_trials_by_more_than_spread": bool(a < b - spread),
+            "rounds_ms": res, "sizes_equal_trial_encodes": same, "bytes_stream0": [int(v) for v in got[0]]}
+
+
+def time_budget(pkg, ctx, ladder, w=1920, h=1080, n=12, rounds=3):
+    """host milliseconds per encode_iframe of one pfv_encoder, i-frame budget off / on (a budget the middle rung meets)"""
+    st = pkg.SyntheticStream(w, h)
+    frs = [pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in range(n)]
+    per = {False: [], True: []}
+    chosen = set()
+    for _ in range(rounds):
+        for on in (False, True):
+            enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, qualities=ladder)
+            budget = int(enc.probe_iframe(frs[0])[len(ladder) // 2])
+            enc.set_rung(len(ladder) // 2)
+            if on:
+                enc.set_iframe_budget(budget)
+            secs = []
+            for fr in frs:
+                t0 = time.perf_counter()
+                enc.encode_iframe(fr)
+                secs.append(time.perf_counter() - t0)
+                chosen.add((on, enc.rung))
+            enc.close()
+            per[on].append(statistics.median(secs[2:]) * 1e3)
+    off, on_ms = statistics.median(per[False]), statistics.median(per[True])
+    return {"shape": f"1 x {w}x{h}", "ladder": ladder, "iframe_ms_budget_off": off, "iframe_ms_budget_on": on_ms, "added_ms": on_ms - off,
+            "rounds_ms": {"off": per[False], "on": per[True]}, "rungs_seen": sorted(chosen)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("width", type=int)
@@ -133,6 +237,7 @@ def main():
     ap.add_argument("--kind", choices=("pan", "low_motion", "static"), default="pan")
     ap.add_argument("--qualities", default="0,2,5,10")
     ap.add_argument("--time-kernel", action="store_true")
+    ap.add_argument("--probe", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -141,6 +246,15 @@ def main():
             print(json.dumps(rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q)), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
+        if a.probe:
+            ladder = [int(x) for x in a.qualities.split(",") if x != ""]
+            print(json.dumps({"probe_sizes": probe_sizes_line(pkg, ctx, a.width, a.height, a.kind, ladder)}), flush=True)
+            if os.environ.get("PFV_HIP_LIB"):          # another build of the C ABI (the CPU emulator): nothing to time
+                return
+            for n_streams in (96, 1):
+                for lad in ([0, 2, 5, 7, 10], list(range(11))):
+                    print(json.dumps({"probe_timing": time_probe(pkg, ctx, n_streams, lad)}), flush=True)
+            print(json.dumps({"probe_budget_latency": time_budget(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
 
 
 if __name__ == "__main__":
