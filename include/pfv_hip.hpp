@@ -170,6 +170,27 @@ class Encoder {
     }
     // byte budget per i-frame payload, 0 = off: encode_iframe takes the finest rung whose probed payload fits, the coarsest if none does
     void set_iframe_budget(uint32_t iframe_budget) { ctx_.check(pfv_encoder_set_iframe_budget(h_, iframe_budget)); }
+    // payload bytes of `f` as a p-frame against the encoder's reference at every rung; nothing changes.  Error(PFV_ERR_STATE) when poisoned or finished
+    std::vector<uint32_t> probe_pframe(const VideoFrame &f) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        ctx_.check(pfv_encoder_probe_pframe(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data()));
+        return sizes;
+    }
+    // on, with a set_rate budget and more than one rung: encode_pframe takes the finest rung whose probed payload fits, the coarsest if none does
+    void set_pframe_probe(bool on) { ctx_.check(pfv_encoder_set_pframe_probe(h_, on ? 1 : 0)); }
+    // encode_frame forces an i-frame once max_interval frames (drop frames included) have followed the last one; 0 = never
+    void set_gop(int max_interval) { ctx_.check(pfv_encoder_set_gop(h_, max_interval)); }
+    // the frame's type chosen by the probes (pfv_encoder_encode_frame) -> 1 i-frame, 2 p-frame, 3 drop frame
+    int encode_frame(const VideoFrame &f)
+    {
+        check_frame(f);
+        int type = 0;
+        ctx_.check(pfv_encoder_encode_frame(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), &type));
+        flush();
+        return type;
+    }
     // of the last encode_* call; Error(PFV_ERR_STATE) when reports are off, nothing has been encoded yet or that call failed
     FrameReport last_report() const
     {

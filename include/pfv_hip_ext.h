@@ -353,6 +353,44 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
  * one-rung encoder has nothing to choose and does not probe. */
 PFV_API int pfv_encoder_set_iframe_budget(pfv_encoder *e, uint32_t iframe_budget);
 
+/* ------------------------------------------------------------------ p-frame size probe, hard p-frame budget, automatic frame type  [B]
+ * payload bytes (the packet adds 5) that pfv_enc_pframe_dev + the entropy stage would produce for these frames against the session's CURRENT
+ * prev_frame at EVERY rung, from one motion search and one forward transform of the residual: the search does not depend on the rung, only
+ * the skip test and the quantiser do.  Reads the tables, the window, the frame stride and prev_frame; changes nothing: prev_frame, the
+ * ping-pong index and the current rung stay as they are.  sizes_dev: uint32[n_streams][n_rungs], entries of slots outside the window left
+ * alone; 0xffffffff = not encodable at that rung.  stats_dev (may be NULL): uint32[n_streams][n_rungs][PFV_PPROBE_STATS] (undefined where
+ * the size is 0xffffffff).  A frame without a coded macroblock has an all-zero histogram and (152 + header bits + 7) / 8 bytes.
+ * Asynchronous on the context's stream; recordable in a graph (the scratch rule of pfv_enc_probe_iframe_dev: the first call allocates, so it
+ * returns PFV_ERR_STATE inside a recording).  Two launches, k_probe_pframe (csrc/pfv_pprobe_kernels.hip) + k_pprobe_sizes; no host-side
+ * clear, no host synchronisation.  One lane mapping, 8 lanes per macroblock: PFV_OPT_LANE_MAPPING does not apply. */
+enum { PFV_PPROBE_STATS = 20 };   /* 16 symbol counts, sum coeff_size, coded mbs, mbs with mv != 0, header bits */
+PFV_API int pfv_enc_probe_pframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev);
+PFV_API int pfv_enc_probe_pframe(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out);      /* host buffers, all slots, packed; synchronises */
+/* pfv_encoder: the same against the encoder's reference; no state changes.  PFV_ERR_STATE when the encoder is poisoned or finished, as
+ * pfv_encoder_encode_pframe. */
+PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/);
+/* Hard p-frame budget, default 0 = off (today's behaviour, byte for byte).  With on != 0, a pfv_encoder_set_rate budget != 0 and more than
+ * one rung, encode_pframe probes the frame first and encodes it at the FINEST rung whose payload is <= the budget (a scan from rung 0; a rung
+ * marked 0xffffffff does not fit), or at the coarsest rung if none fits; that rung becomes the current rung and the soft rule of
+ * pfv_encoder_set_rate is not applied while the probe is on.  Costs one launch pair, one 4 * n_rungs-byte download and one synchronisation
+ * per p-frame, on both entropy paths; the frame goes up once. */
+PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on);
+/* pfv_encoder_encode_frame chooses the frame's type; *type_out (may be NULL): 1 i-frame, 2 p-frame, 3 drop frame.  In this order:
+ *   1. a forced i-frame (encode_iframe's path, i-frame budget included) when no frame has been written yet, or the encoder is poisoned, or
+ *      max_interval > 0 (pfv_encoder_set_gop; default 0 = never; < 0: PFV_ERR_BAD_ARG) and max_interval frames, drop frames included, have
+ *      followed the last i-frame;
+ *   2. the frame goes up once and is sized as a p-frame; rp = the hard budget's rung where that applies, else the current rung;
+ *   3. no coded macroblock at rp and no non-zero vector: a drop frame (it shows the frame that p-frame would show and leaves the same
+ *      reference); the rung stays;
+ *   4. the frame is sized as an i-frame from the same upload; isize[rp] <= psize[rp]: an i-frame, its rung chosen as encode_iframe does;
+ *   5. otherwise a p-frame at rp, which becomes the current rung.
+ * Costs per frame behind the first: up to two launch pairs, two downloads of at most 84 * n_rungs and 4 * n_rungs bytes, each with its
+ * synchronisation, before the encode itself.  Rule 4 means what it says and is NOT a scene-cut detector: residuals are halved
+ * (src/common.rs:118-119, :304), so a p-frame across a cut is often the smaller one (texture, noise) and is then written.  Frame reports
+ * work as for the explicit calls.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have none of this. */
+PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval);
+PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out /* 1 i, 2 p, 3 drop */);
+
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);
  * every writer receives exactly the bytes an Encoder of its own would have written.  Per frame step: ONE upload of all

@@ -170,6 +170,12 @@ SIGNATURES = [
     ("pfv_enc_probe_iframe", c_int, [_P, _P, _P]),
     ("pfv_encoder_probe_iframe", c_int, [_P, _P, _P, _P, _P]),
     ("pfv_encoder_set_iframe_budget", c_int, [_P, ctypes.c_uint32]),
+    ("pfv_enc_probe_pframe_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_enc_probe_pframe", c_int, [_P, _P, _P]),
+    ("pfv_encoder_probe_pframe", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_encoder_set_pframe_probe", c_int, [_P, c_int]),
+    ("pfv_encoder_set_gop", c_int, [_P, c_int]),
+    ("pfv_encoder_encode_frame", c_int, [_P, _P, _P, _P, _P]),
     ("pfv_batch_encoder_create", c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, POINTER(_P)]),
     ("pfv_batch_encoder_frames", _P, [_P]),
     ("pfv_batch_encoder_encode", c_int, [_P, c_int, _P]),

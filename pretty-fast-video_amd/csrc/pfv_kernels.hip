@@ -1186,6 +1186,7 @@ __device__ __forceinline__ void issue_window(const PlaneGeom &p, const uint8_t *
 // Result of the search phase of one macroblock (identical in its 8 lanes) plus the lane's patch rows.
 struct SearchOut {
     int cx, cy;
+    int err;            // best_err of the chosen vector; only k_probe_pframe reads it (dead and removed in the encode kernels)
     bool coded;
     uint4 patch[2];
 };
@@ -1240,6 +1241,7 @@ __device__ __forceinline__ void penc_search(const FrameGeom &g, const TilePos &t
     // skip decision (src/common.rs:209, :221): best_err <= px_err^2 * 256, compared in f32
     so.coded = mb_valid && !((float)st.err <= min_err);
     so.cx = st.cx; so.cy = st.cy;
+    so.err = st.err;
 
     // the lane's two rows of the chosen patch (get_block of the reconstruction, :261)
     const int wx = wcol0 + st.cx, shp = wx & 3;

@@ -23,6 +23,7 @@
 //                     per wavefront  the lanes' counts -- sixteen 8-bit fields, sizes and runs together; sumsize = four v_dot4 over the size
 //                                 fields -- are widened to 16-bit fields, summed over each 16-lane row with DPP and over the four rows on the
 //                                 scalar side, and seventeen lanes add them to acc[stream][rung] with one vector atomic.
+//   probe_rung_loop the "per rung" part above as a device function: k_probe_pframe (pfv_pprobe_kernels.hip) runs it on residuals.
 //   k_probe_sizes   one wavefront per (stream, rung): ent_build_codes_wave on the 16 counts, the size, and the accumulator cleared for the next
 //                   call -- so a call needs no host-side clear and no host synchronisation, and a recorded pair of launches can be replayed.
 // Included by pfv_capi.hip behind pfv_entropy_kernels.hip.
@@ -36,6 +37,8 @@ namespace pfv {
 constexpr int kProbeMaxRungs = 11;     // a ladder has at most this many rungs (pfv_enc_session_create_ladder)
 constexpr int kProbeStats = 17;        // per (stream, rung): 16 symbol counts + the sum of coefficient sizes
 constexpr int kProbeAcc = 18;          // the accumulator's row: the same + the oversize flag
+// the p-frame probe's row: the same counts + coded macroblocks, macroblocks with a non-zero vector, block-header bits; then the oversize flag
+constexpr int kPProbeStats = 20, kPProbeAcc = 21, kPProbeCodedAt = 17, kPProbeMovedAt = 18, kPProbeHdrAt = 19;
 constexpr uint32_t kProbeOversizeExp = 127u + 14u;   // |q| >= 2^14: coeff_size >= 16 (rle.rs:44 would panic; kEntErrOversize)
 constexpr uint64_t kNibbleEven = 0x0f0f0f0f0f0f0f0full;
 
@@ -113,6 +116,99 @@ __device__ __forceinline__ void probe_runs(const uint32_t (&words)[8], int lane,
     od += ((rest4 >> 4) & kNibbleEven) + ((uint64_t)n_fill << 56);   // bin 15: the fillers
 }
 
+// The rung loop of the size probes (k_probe_iframe, k_probe_pframe): nn = the lane's scaled coefficients, zz = their zigzag positions, rcp = the
+// reciprocals of all rungs [n_rungs][64] (LDS), rows = the accumulator rows of the wavefront's stream (PITCH words per rung, the oversize flag
+// at word FLAG_AT); counts(r): the lane's macroblock is written at rung r (an i-frame: it exists; a p-frame: it exists and is coded there).
+template <int LPM, int PITCH, int FLAG_AT, class Counts>
+__device__ __forceinline__ void probe_rung_loop(const f2 (&nn)[LPM == 8 ? 2 : 1][8], const int (&zz)[8], const float *rcp, int n_rungs, int lane,
+                                                uint32_t *__restrict__ rows, Counts &&counts)
+{
+    constexpr int kPasses = LPM == 8 ? 2 : 1;
+    const int slot = lane >> 3, i = lane & 7;
+    for (int r = 0; r < n_rungs; r++) {
+        const float *rc = rcp + 64 * r;
+        uint64_t nzmap[kPasses][2], size4[kPasses][2];   // per subblock: the lane's part of the non-zero map; sixteen 4-bit size counters
+        uint32_t emax = 0;
+#pragma unroll
+        for (int pass = 0; pass < kPasses; pass++) {
+            nzmap[pass][0] = nzmap[pass][1] = size4[pass][0] = size4[pass][1] = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const f2 q = f2trunc(nn[pass][k] * f2s(rc[k * 8 + i]));   // quant_div: n / q, truncating
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    const uint32_t e = ((uint32_t)__float_as_int(q[s]) >> 23) & 0xffu;
+                    const uint64_t nz = (uint64_t)min(e, 1u);
+                    emax = max(emax, e);
+                    nzmap[pass][s] |= nz << zz[k];
+                    size4[pass][s] += nz << ((4u * e - 500u) & 63u);   // bin coeff_size = e - 125
+                }
+            }
+        }
+        // the macroblock's map in all of its lanes
+        uint32_t words[8];
+        if (LPM == 8) {
+#pragma unroll
+            for (int pass = 0; pass < kPasses; pass++)
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    words[4 * pass + 2 * s] = probe_mb_or((uint32_t)nzmap[pass][s]);
+                    words[4 * pass + 2 * s + 1] = probe_mb_or((uint32_t)(nzmap[pass][s] >> 32));
+                }
+        } else {   // the slot holds subblocks 2h, 2h + 1; the other half lies 8 lanes away
+            const bool upper = (slot & 1) != 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t mine = probe_mb_or((uint32_t)(nzmap[0][j >> 1] >> (32 * (j & 1))));
+                const uint32_t other = (uint32_t)dpp<kRowRor8>((int)mine);
+                words[j] = upper ? other : mine;
+                words[4 + j] = upper ? mine : other;
+            }
+        }
+        uint64_t ev = 0, od = 0;
+#pragma unroll
+        for (int pass = 0; pass < kPasses; pass++)
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                ev += size4[pass][s] & kNibbleEven;
+                od += (size4[pass][s] >> 4) & kNibbleEven;
+            }
+        // sum of coeff_size: bin x count over the size counters alone, before the run symbols join them
+        uint32_t sumsize = __builtin_amdgcn_udot4((uint32_t)ev, 0x06040200u, 0u, false);
+        sumsize = __builtin_amdgcn_udot4((uint32_t)(ev >> 32), 0x0e0c0a08u, sumsize, false);
+        sumsize = __builtin_amdgcn_udot4((uint32_t)od, 0x07050301u, sumsize, false);
+        sumsize = __builtin_amdgcn_udot4((uint32_t)(od >> 32), 0x0f0d0b09u, sumsize, false);
+        probe_runs<LPM>(words, lane, ev, od);
+        const bool present = counts(r);
+        if (!present) { ev = od = 0; sumsize = 0; }
+
+        // 8-bit fields (a lane's count stays below 96) -> 16-bit fields (a wavefront's below 64 * 96), d[2 a + b]: bytes b and b + 2 of dword a
+        const uint32_t x[4] = {(uint32_t)ev, (uint32_t)(ev >> 32), (uint32_t)od, (uint32_t)(od >> 32)};
+        uint32_t tot[8];
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++) {
+                const uint32_t d = ent_row_sum((x[a] >> (8 * b)) & 0x00ff00ffu);
+                tot[2 * a + b] = (uint32_t)(__builtin_amdgcn_readlane((int)d, 0) + __builtin_amdgcn_readlane((int)d, 16) + __builtin_amdgcn_readlane((int)d, 32) +
+                                            __builtin_amdgcn_readlane((int)d, 48));
+            }
+        const uint32_t ss = ent_row_sum(sumsize);
+        const uint32_t ss_tot = (uint32_t)(__builtin_amdgcn_readlane((int)ss, 0) + __builtin_amdgcn_readlane((int)ss, 16) + __builtin_amdgcn_readlane((int)ss, 32) +
+                                           __builtin_amdgcn_readlane((int)ss, 48));
+        // lane k < 16: bin k = byte k / 2 of ev (k even) or od (k odd); lane 16: the size sum
+        const int byte = lane >> 1, sel = (lane & 1) * 4 + (byte >> 2) * 2 + (byte & 1);
+        uint32_t mine = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) mine = sel == j ? tot[j] : mine;
+        mine = (byte & 2) ? mine >> 16 : mine & 0xffffu;
+        if (lane == 16) mine = ss_tot;
+        uint32_t *row = rows + (size_t)r * PITCH;
+        if (lane < kProbeStats && mine) atomicAdd(&row[lane], mine);
+        if (__any(present && emax >= kProbeOversizeExp) && lane == 0) atomicOr(&row[FLAG_AT], 1u);
+    }
+}
+
 template <bool FLT, int LPM = 8>
 __global__ __launch_bounds__(kThreads) void k_probe_iframe(FrameGeom g, const uint8_t *__restrict__ src, const QTab *__restrict__ qtabs, int n_rungs,
                                                             uint32_t *__restrict__ acc)
@@ -182,113 +278,51 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe(FrameGeom g, const ui
 #pragma unroll
     for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
     const bool present = m < sp.n_mb;   // macroblocks beyond the strip's end count nothing
-
-    for (int r = 0; r < n_rungs; r++) {
-        const float *rc = rcp_lds[wave][r];
-        uint64_t nzmap[kPasses][2], size4[kPasses][2];   // per subblock: the lane's part of the non-zero map; sixteen 4-bit size counters
-        uint32_t emax = 0;
-#pragma unroll
-        for (int pass = 0; pass < kPasses; pass++) {
-            nzmap[pass][0] = nzmap[pass][1] = size4[pass][0] = size4[pass][1] = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const f2 q = f2trunc(nn[pass][k] * f2s(rc[k * 8 + i]));   // quant_div: n / q, truncating
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    const uint32_t e = ((uint32_t)__float_as_int(q[s]) >> 23) & 0xffu;
-                    const uint64_t nz = (uint64_t)min(e, 1u);
-                    emax = max(emax, e);
-                    nzmap[pass][s] |= nz << zz[k];
-                    size4[pass][s] += nz << ((4u * e - 500u) & 63u);   // bin coeff_size = e - 125
-                }
-            }
-        }
-        // the macroblock's map in all of its lanes
-        uint32_t words[8];
-        if (LPM == 8) {
-#pragma unroll
-            for (int pass = 0; pass < kPasses; pass++)
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    words[4 * pass + 2 * s] = probe_mb_or((uint32_t)nzmap[pass][s]);
-                    words[4 * pass + 2 * s + 1] = probe_mb_or((uint32_t)(nzmap[pass][s] >> 32));
-                }
-        } else {   // the slot holds subblocks 2h, 2h + 1; the other half lies 8 lanes away
-            const bool upper = (slot & 1) != 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t mine = probe_mb_or((uint32_t)(nzmap[0][j >> 1] >> (32 * (j & 1))));
-                const uint32_t other = (uint32_t)dpp<kRowRor8>((int)mine);
-                words[j] = upper ? other : mine;
-                words[4 + j] = upper ? mine : other;
-            }
-        }
-        uint64_t ev = 0, od = 0;
-#pragma unroll
-        for (int pass = 0; pass < kPasses; pass++)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                ev += size4[pass][s] & kNibbleEven;
-                od += (size4[pass][s] >> 4) & kNibbleEven;
-            }
-        // sum of coeff_size: bin x count over the size counters alone, before the run symbols join them
-        uint32_t sumsize = __builtin_amdgcn_udot4((uint32_t)ev, 0x06040200u, 0u, false);
-        sumsize = __builtin_amdgcn_udot4((uint32_t)(ev >> 32), 0x0e0c0a08u, sumsize, false);
-        sumsize = __builtin_amdgcn_udot4((uint32_t)od, 0x07050301u, sumsize, false);
-        sumsize = __builtin_amdgcn_udot4((uint32_t)(od >> 32), 0x0f0d0b09u, sumsize, false);
-        probe_runs<LPM>(words, lane, ev, od);
-        if (!present) { ev = od = 0; sumsize = 0; }
-
-        // 8-bit fields (a lane's count stays below 96) -> 16-bit fields (a wavefront's below 64 * 96), d[2 a + b]: bytes b and b + 2 of dword a
-        const uint32_t x[4] = {(uint32_t)ev, (uint32_t)(ev >> 32), (uint32_t)od, (uint32_t)(od >> 32)};
-        uint32_t tot[8];
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++) {
-                const uint32_t d = ent_row_sum((x[a] >> (8 * b)) & 0x00ff00ffu);
-                tot[2 * a + b] = (uint32_t)(__builtin_amdgcn_readlane((int)d, 0) + __builtin_amdgcn_readlane((int)d, 16) + __builtin_amdgcn_readlane((int)d, 32) +
-                                            __builtin_amdgcn_readlane((int)d, 48));
-            }
-        const uint32_t ss = ent_row_sum(sumsize);
-        const uint32_t ss_tot = (uint32_t)(__builtin_amdgcn_readlane((int)ss, 0) + __builtin_amdgcn_readlane((int)ss, 16) + __builtin_amdgcn_readlane((int)ss, 32) +
-                                           __builtin_amdgcn_readlane((int)ss, 48));
-        // lane k < 16: bin k = byte k / 2 of ev (k even) or od (k odd); lane 16: the size sum
-        const int byte = lane >> 1, sel = (lane & 1) * 4 + (byte >> 2) * 2 + (byte & 1);
-        uint32_t mine = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) mine = sel == j ? tot[j] : mine;
-        mine = (byte & 2) ? mine >> 16 : mine & 0xffffu;
-        if (lane == 16) mine = ss_tot;
-        uint32_t *row = acc + ((size_t)sp.stream * n_rungs + r) * kProbeAcc;
-        if (lane < kProbeStats && mine) atomicAdd(&row[lane], mine);
-        if (__any(present && emax >= kProbeOversizeExp) && lane == 0) atomicOr(&row[kProbeStats], 1u);
-    }
+    probe_rung_loop<LPM, kProbeAcc, kProbeStats>(nn, zz, &rcp_lds[wave][0][0], n_rungs, lane, acc + (size_t)sp.stream * n_rungs * kProbeAcc,
+                                                 [&](int) { return present; });
 }
 
-// One wavefront per (stream, rung): acc rows in, sizes (and the counts, where asked for) out, acc rows cleared.
+// One wavefront per (stream, rung): acc rows in, sizes (and the counts, where asked for) out, acc rows cleared.  PFRAME: the rows of
+// k_probe_pframe (pfv_pprobe_kernels.hip) -- three more counts, of which the block-header bits join the size.  The body of both kernels; the LDS
+// arrays are theirs (function-local to a plain kernel, so the compiler can drop the ones ent_build_codes_wave only writes).
+template <bool PFRAME>
+__device__ __forceinline__ void probe_sizes_row(uint32_t *__restrict__ acc, uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats, int32_t *hist, uint8_t *table,
+                                                uint32_t *val, uint8_t *len, int *parent, int *branch)
+{
+    constexpr int kAcc = PFRAME ? kPProbeAcc : kProbeAcc, kStats = PFRAME ? kPProbeStats : kProbeStats;
+    const int lane = (int)threadIdx.x;
+    const size_t e = blockIdx.x;
+    uint32_t *row = acc + e * kAcc;
+    uint32_t mine = 0;
+    if (lane < kAcc) {
+        mine = row[lane];
+        row[lane] = 0;   // consumed: the next call starts clean
+    }
+    if (lane < 16) hist[lane] = (int32_t)mine;
+    if (stats && lane < kStats) stats[e * kStats + lane] = mine;
+    ent_wave_lds_sync();
+    ent_build_codes_wave(hist, table, val, len, parent, branch);
+    ent_wave_lds_sync();
+    const uint32_t bits = ent_wave_sum(lane < 16 ? mine * (uint32_t)len[lane] : 0u);
+    const uint32_t sumsize = ent_shfl(mine, 16), oversize = ent_shfl(mine, kStats);
+    const uint32_t hdr_bits = PFRAME ? ent_shfl(mine, kPProbeHdrAt) : 0u;   // 2 per macroblock, 16 where the vector is non-zero (k_ent_scan)
+    if (lane == 0) sizes[e] = oversize ? kEntErrOversize : (19u * 8u + hdr_bits + bits + sumsize + 7u) >> 3;   // as k_ent_codes: 16 table bytes + 3 q indices first
+}
 __global__ __launch_bounds__(64) void k_probe_sizes(uint32_t *__restrict__ acc, uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats)
 {
     __shared__ int32_t hist[16];
     __shared__ uint32_t val[16];
     __shared__ uint8_t len[16], table[16];
     __shared__ int parent[32], branch[32];
-    const int lane = (int)threadIdx.x;
-    const size_t e = blockIdx.x;
-    uint32_t *row = acc + e * kProbeAcc;
-    uint32_t mine = 0;
-    if (lane < kProbeAcc) {
-        mine = row[lane];
-        row[lane] = 0;   // consumed: the next call starts clean
-    }
-    if (lane < 16) hist[lane] = (int32_t)mine;
-    if (stats && lane < kProbeStats) stats[e * kProbeStats + lane] = mine;
-    ent_wave_lds_sync();
-    ent_build_codes_wave(hist, table, val, len, parent, branch);
-    ent_wave_lds_sync();
-    const uint32_t bits = ent_wave_sum(lane < 16 ? mine * (uint32_t)len[lane] : 0u);
-    const uint32_t sumsize = ent_shfl(mine, 16), oversize = ent_shfl(mine, 17);
-    if (lane == 0) sizes[e] = oversize ? kEntErrOversize : (19u * 8u + bits + sumsize + 7u) >> 3;   // as k_ent_codes: 16 table bytes + 3 q indices first
+    probe_sizes_row<false>(acc, sizes, stats, hist, table, val, len, parent, branch);
+}
+__global__ __launch_bounds__(64) void k_pprobe_sizes(uint32_t *__restrict__ acc, uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats)
+{
+    __shared__ int32_t hist[16];
+    __shared__ uint32_t val[16];
+    __shared__ uint8_t len[16], table[16];
+    __shared__ int parent[32], branch[32];
+    probe_sizes_row<true>(acc, sizes, stats, hist, table, val, len, parent, branch);
 }
 
 }  // namespace pfv

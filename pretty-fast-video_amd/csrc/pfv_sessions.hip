@@ -108,6 +108,10 @@ struct pfv_enc_session {
     // i-frame size probe (pfv_probe.hip): the kernels' accumulator [n_streams][n_rungs][kProbeAcc], zero between calls; sizes of the host-buffer form
     uint32_t *probe_acc = nullptr;
     uint32_t *probe_sizes = nullptr;
+    // p-frame size probe (pfv_pprobe.hip): accumulator [n_streams][n_rungs][kPProbeAcc], zero between calls, with min_err of every rung behind it;
+    // sizes [n_streams][n_rungs] and counts [n_streams][n_rungs][kPProbeStats] of the host-buffer form
+    uint32_t *pprobe_acc = nullptr;
+    uint32_t *pprobe_out = nullptr;
     // device entropy stage (pfv_enc_entropy_enable)
     bool ent_on = false;
     uint32_t ent_cap = 0;
@@ -227,7 +231,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->pprobe_acc, s->pprobe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -359,19 +363,18 @@ PFV_API int pfv_enc_iframe(pfv_enc_session *s, const uint8_t *frames, int16_t *c
     return enc_iframe_host(s, frames, coef_out);
 }
 
-PFV_API int pfv_enc_pframe(pfv_enc_session *s, const uint8_t *frames, int8_t *mv_out, uint8_t *has_coef_out,
-                           int16_t *coef_out)
+// frames == nullptr: they lie in the session's frame staging already (pfv_encoder's p-frame probe has sized them there)
+static int enc_pframe_host(pfv_enc_session *s, const uint8_t *frames, int8_t *mv_out, uint8_t *has_coef_out, int16_t *coef_out)
 {
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
     pfv_ctx *ctx = s->ctx;
-    if (!frames || !mv_out || !has_coef_out || !coef_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_pframe: null buffer");
     if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, "pfv_enc_pframe: the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = enc_staging(s);
     if (rc) return rc;
     size_t n = (size_t)s->geom.mbs_per_frame * s->n_streams;
-    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
-                                hipMemcpyHostToDevice, ctx->stream));
+    if (frames)
+        HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams,
+                                    hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_pframe_dev(s, s->st_frames, s->st_mv, s->st_has, s->st_coef))) return rc;
     if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
@@ -379,6 +382,14 @@ PFV_API int pfv_enc_pframe(pfv_enc_session *s, const uint8_t *frames, int8_t *mv
     HIP_TRY(ctx, hipMemcpyAsync(has_coef_out, s->st_has, n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
+}
+
+PFV_API int pfv_enc_pframe(pfv_enc_session *s, const uint8_t *frames, int8_t *mv_out, uint8_t *has_coef_out,
+                           int16_t *coef_out)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    if (!frames || !mv_out || !has_coef_out || !coef_out) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_pframe: null buffer");
+    return enc_pframe_host(s, frames, mv_out, has_coef_out, coef_out);
 }
 
 PFV_API const uint8_t *pfv_enc_prev_frame_dev(pfv_enc_session *s, int stream)

@@ -79,6 +79,11 @@ struct pfv_encoder {
     int last_rung = -1;                    // rung of the last frame written (-1: none yet)
     uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
     uint32_t budget_i = 0;                 // i-frame payload bytes (pfv_encoder_set_iframe_budget); 0: off
+    // p-frame size probe (pfv_encoder_set_pframe_probe): the hard p-frame budget; automatic frame types (pfv_encoder_encode_frame)
+    bool pprobe_on = false;
+    int gop_max = 0;                       // pfv_encoder_set_gop: an i-frame is forced once this many frames have followed the last one; 0: never
+    uint64_t n_written = 0;                // frames written, drop frames included
+    int since_iframe = 0;                  // frames written behind the last i-frame, drop frames included
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -594,7 +599,9 @@ static void rate_frame_written(pfv_encoder *e, bool pframe, size_t payload_bytes
 {
     pfv_enc_session *s = e->hot;
     e->last_rung = s->rung;
-    if (!pframe || !e->budget_p) return;
+    e->n_written++;
+    e->since_iframe = pframe ? e->since_iframe + 1 : 0;
+    if (!pframe || !e->budget_p || e->pprobe_on) return;   // with the probe on the budget is the hard one: the rung was chosen before the frame was written
     if (payload_bytes > e->budget_p) s->rung = std::min(s->rung + 1, s->n_rungs - 1);
     else if (2 * (uint64_t)payload_bytes <= e->budget_p) s->rung = std::max(s->rung - 1, 0);
 }
@@ -674,36 +681,39 @@ PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out)
     return PFV_OK;
 }
 
+// the finest rung whose probed payload fits `budget`: the scan starts at rung 0, a rung marked not encodable does not fit, the coarsest if none does
+static int budget_rung(const pfv_enc_session *s, const uint32_t *sizes, uint32_t budget)
+{
+    for (int r = 0; r < s->n_rungs; r++)
+        if (sizes[r] != kEntErrOversize && sizes[r] <= budget) return r;
+    return s->n_rungs - 1;
+}
 // The i-frame byte budget: the frame goes up into the session's staging, the probe sizes it at every rung, and the finest rung whose payload
 // fits becomes the current rung (the coarsest if none does; a rung the probe marks not encodable does not fit).
-static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+// staged: the frame lies in the session's staging already; probed: ... and these are its i-frame sizes (pfv_encoder_encode_frame)
+static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged, const uint32_t *probed)
 {
     pfv_enc_session *s = e->hot;
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(s);
-    if (!rc) rc = upload_planes(e, y, u, v);
+    if (!rc && !staged) rc = upload_planes(e, y, u, v);
     uint32_t sizes[kMaxRungs];
-    if (!rc) rc = probe_staged(s, sizes);
+    if (!rc && !probed) rc = probe_staged(s, sizes);
     if (rc) return rc;
-    int rung = s->n_rungs - 1;
-    for (int r = 0; r < s->n_rungs; r++)
-        if (sizes[r] != kEntErrOversize && sizes[r] <= e->budget_i) { rung = r; break; }
-    s->rung = rung;
+    s->rung = budget_rung(s, probed ? probed : sizes, e->budget_i);
     return PFV_OK;
 }
 
-// Encoder::encode_iframe (src/enc.rs:75-123)
-PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+// Encoder::encode_iframe (src/enc.rs:75-123) behind pack_frame.  staged / probed: see choose_iframe_rung
+static int write_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false, const uint32_t *probed = nullptr)
 {
-    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (e->report_on) e->report_state = -1;   // until this call has written its packet
-    int rc = pack_frame(e, y, u, v);
-    if (rc) return rc;
+    int rc;
     const bool budget = e->budget_i != 0 && e->hot->n_rungs > 1;   // one rung: nothing to choose
-    if (budget && (rc = choose_iframe_rung(e, y, u, v))) return rc;
-    if (e->device_entropy) return encode_on_device(e, false, budget);      // an i-frame replaces prev_frame entirely: clears a poisoned state
+    if (budget && (rc = choose_iframe_rung(e, y, u, v, staged, probed))) return rc;
+    staged = staged || budget;
+    if (e->device_entropy) return encode_on_device(e, false, staged);      // an i-frame replaces prev_frame entirely: clears a poisoned state
     if ((rc = host_entropy_staging(e))) return rc;
-    if ((rc = enc_iframe_host(e->hot, budget ? nullptr : e->frame.data(), e->coef.data()))) return rc;
+    if ((rc = enc_iframe_host(e->hot, staged ? nullptr : e->frame.data(), e->coef.data()))) return rc;
     e->poisoned = true;
     std::vector<uint8_t> payload;
     const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung), (uint8_t)(4 * e->hot->rung + 1), (uint8_t)(4 * e->hot->rung + 1)};
@@ -714,6 +724,14 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     fill_report(e, 1, 5 + payload.size());
     rate_frame_written(e, false, payload.size());
     return PFV_OK;
+}
+PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    int rc = pack_frame(e, y, u, v);
+    if (rc) return rc;
+    return write_iframe(e, y, u, v);
 }
 // payload bytes of this frame as an i-frame at every rung; the encoder's stream, reference and rung stay as they are
 PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out)
@@ -726,19 +744,54 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
     if (!rc) rc = probe_staged(e->hot, sizes_out);
     return rc;
 }
-// Encoder::encode_pframe (src/enc.rs:125-173)
-PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+// the frame up into the session's staging and sized as a p-frame at every rung (counts: [n_rungs][kPProbeStats], or nullptr)
+static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts)
+{
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    int rc = enc_staging(e->hot);
+    if (!rc) rc = upload_planes(e, y, u, v);
+    if (!rc) rc = pprobe_staged(e->hot, sizes, counts);
+    return rc;
+}
+// payload bytes of this frame as a p-frame against the encoder's reference at every rung; the stream, the reference and the rung stay as they are
+PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (e->report_on) e->report_state = -1;   // until this call has written its packet
-    int rc = pack_frame(e, y, u, v);
-    if (rc) return rc;
-    // a previous frame failed after the encoder's reference had advanced but before its packet was written: a p-frame
-    // now would predict from a frame the decoder never saw (the reference panics in that situation and the Encoder is gone)
+    if (!y || !u || !v || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe: null buffer");
+    if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
-    if (e->device_entropy) return encode_on_device(e, true);
+    return probe_pframe_planes(e, y, u, v, sizes_out, nullptr);
+}
+PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    e->pprobe_on = on != 0;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (max_interval < 0) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_gop: max_interval must be >= 0");
+    e->gop_max = max_interval;
+    return PFV_OK;
+}
+// the hard p-frame budget applies: the probe is on, a budget is set and there is a rung to choose
+static bool hard_pframe_budget(const pfv_encoder *e) { return e->pprobe_on && e->budget_p != 0 && e->hot->n_rungs > 1; }
+
+// Encoder::encode_pframe (src/enc.rs:125-173) behind pack_frame and the poisoned test.  staged: the frame lies in the session's staging and the
+// rung is settled (pfv_encoder_encode_frame); otherwise the hard budget, where it applies, probes the frame and chooses the rung first.
+static int write_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false)
+{
+    int rc;
+    if (!staged && hard_pframe_budget(e)) {
+        uint32_t sizes[kMaxRungs];
+        if ((rc = probe_pframe_planes(e, y, u, v, sizes, nullptr))) return rc;
+        e->hot->rung = budget_rung(e->hot, sizes, e->budget_p);
+        staged = true;
+    }
+    if (e->device_entropy) return encode_on_device(e, true, staged);
     if ((rc = host_entropy_staging(e))) return rc;
-    if ((rc = pfv_enc_pframe(e->hot, e->frame.data(), e->mv.data(), e->has.data(), e->coef.data()))) return rc;
+    if ((rc = enc_pframe_host(e->hot, staged ? nullptr : e->frame.data(), e->mv.data(), e->has.data(), e->coef.data()))) return rc;
     e->poisoned = true;
     std::vector<uint8_t> payload;
     const uint8_t qidx[3] = {(uint8_t)(4 * e->hot->rung + 2), (uint8_t)(4 * e->hot->rung + 3), (uint8_t)(4 * e->hot->rung + 3)};
@@ -750,14 +803,64 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
     rate_frame_written(e, true, payload.size());
     return PFV_OK;
 }
+PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    int rc = pack_frame(e, y, u, v);
+    if (rc) return rc;
+    // a previous frame failed after the encoder's reference had advanced but before its packet was written: a p-frame
+    // now would predict from a frame the decoder never saw (the reference panics in that situation and the Encoder is gone)
+    if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    return write_pframe(e, y, u, v);
+}
+static void write_dropframe(pfv_encoder *e)
+{
+    put_packet(e->out, 1, nullptr, 0);
+    fill_report(e, 3, 5);
+    e->n_written++;
+    e->since_iframe++;
+}
+// The frame's type chosen by the probes; the rules, in this order, are at the declaration (include/pfv_hip_ext.h)
+PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    int rc = pack_frame(e, y, u, v);
+    if (rc) return rc;
+    pfv_enc_session *s = e->hot;
+    int type = 1;
+    if (e->n_written == 0 || e->poisoned || (e->gop_max > 0 && e->since_iframe >= e->gop_max)) {   // 1: a forced i-frame
+        rc = write_iframe(e, y, u, v);
+    } else {
+        uint32_t psize[kMaxRungs], isize[kMaxRungs], counts[kMaxRungs][kPProbeStats];
+        if ((rc = probe_pframe_planes(e, y, u, v, psize, &counts[0][0]))) return rc;                // 2: one upload, the p-frame sized at every rung
+        const int rp = hard_pframe_budget(e) ? budget_rung(s, psize, e->budget_p) : s->rung;
+        if (counts[rp][kPProbeCodedAt] == 0 && counts[rp][kPProbeMovedAt] == 0) {                   // 3: nothing to code, nothing moved: a drop frame
+            type = 3;
+            write_dropframe(e);
+        } else {
+            if ((rc = probe_staged(s, isize))) return rc;                                          // 4: an i-frame that is not larger at rp
+            // psize[rp] marked not encodable (0xffffffff) compares as larger than any i-frame that is encodable: the i-frame is taken
+            if (isize[rp] != kEntErrOversize && isize[rp] <= psize[rp]) {
+                rc = write_iframe(e, y, u, v, true, isize);
+            } else {                                                                                // 5: a p-frame at rp
+                type = 2;
+                s->rung = rp;
+                rc = write_pframe(e, y, u, v, true);
+            }
+        }
+    }
+    if (!rc && type_out) *type_out = type;
+    return rc;
+}
 // Encoder::encode_dropframe (src/enc.rs:175-180): an i-frame packet with an empty payload
 PFV_API int pfv_encoder_encode_dropframe(pfv_encoder *e)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:176)");
-    put_packet(e->out, 1, nullptr, 0);
-    fill_report(e, 3, 5);
+    write_dropframe(e);
     return PFV_OK;
 }
 // Encoder::finish (src/enc.rs:182-188): EOF packet

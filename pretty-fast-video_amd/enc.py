@@ -107,6 +107,33 @@ class Encoder:
                                                               ptr(frame.plane_v.pixels), ptr(sizes)))
         return sizes
 
+    def probe_pframe(self, frame: VideoFrame):
+        """payload bytes of `frame` as a p-frame against the encoder's reference at every rung, uint32 [n_rungs] (0xffffffff: not encodable at
+        that rung); the stream, the reference and the rung stay as they are.  PfvError(PFV_ERR_STATE) when poisoned or finished"""
+        import numpy as np
+        sizes = np.zeros(self.n_rungs, dtype=np.uint32)
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
+                                                              ptr(frame.plane_v.pixels), ptr(sizes)))
+        return sizes
+
+    def set_pframe_probe(self, on: bool = True):
+        """on, with a set_rate budget and more than one rung: encode_pframe probes the frame and encodes it at the finest rung whose payload
+        fits the budget, the coarsest if none does -- a hard budget instead of set_rate's soft rule (pfv_encoder_set_pframe_probe)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_pframe_probe(self.handle, 1 if on else 0))
+
+    def set_gop(self, max_interval: int = 0):
+        """encode_frame forces an i-frame once `max_interval` frames (drop frames included) have followed the last one; 0: never"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_gop(self.handle, int(max_interval)))
+
+    def encode_frame(self, frame: VideoFrame) -> int:
+        """the frame's type chosen by the probes (pfv_encoder_encode_frame, include/pfv_hip_ext.h) -> 1 i-frame, 2 p-frame, 3 drop frame"""
+        self._check_frame(frame)
+        t = ctypes.c_int(0)
+        self.ctx.check(self.ctx._lib.pfv_encoder_encode_frame(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
+                                                              ptr(frame.plane_v.pixels), ctypes.byref(t)))
+        self._flush()
+        return int(t.value)
+
     @property
     def last_report(self):
         """FrameReport of the last encode_* call (pfv_encoder_frame_report); PfvError(PFV_ERR_STATE) when reports are off, nothing has

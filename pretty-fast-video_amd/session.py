@@ -88,6 +88,22 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_probe_iframe_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
                                                               ctypes.c_void_p(stats_dev or 0)))
 
+    # p-frame size probe -------------------------------------------------
+    def probe_pframe(self, frames) -> np.ndarray:
+        """payload bytes of every stream's frame as a p-frame against the current prev_frame at every rung, uint32 [n_streams, n_rungs], from
+        one search and one transform (pfv_enc_probe_pframe); 0xffffffff: not encodable at that rung.  Leaves prev_frame and the rung alone."""
+        f = self._frames(frames)
+        sizes = np.zeros((self.n_streams, self.n_rungs), dtype=np.uint32)
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe(self.handle, ptr(f), ptr(sizes)))
+        return sizes
+
+    def probe_pframe_dev(self, frames_dev: int, sizes_dev: int, stats_dev: int = 0):
+        """asynchronous on the context's stream; sizes_dev uint32 [n_streams][n_rungs], stats_dev uint32 [n_streams][n_rungs][20] or 0 (16
+        symbol counts, sum of coefficient sizes, coded macroblocks, macroblocks with a non-zero vector, header bits).  Honours the window and
+        the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
+                                                              ctypes.c_void_p(stats_dev or 0)))
+
     # host-buffer forms ------------------------------------------------
     def _frames(self, frames) -> np.ndarray:
         f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)

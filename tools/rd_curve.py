@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -19,6 +19,12 @@ ladders 0,2,5,7,10 and 0..10.  B twice: with the stage as a caller runs it (all 
 where k_ent_init / k_ent_pack leave at once -- the stage "up to the size" (k_ent_scan + k_ent_codes), B's lower bound.  HIP events on the
 context's stream, warm-up, A and B alternating in one process, medians; the whole comparison three times for B's own spread.  Last the
 latency an i-frame budget adds to one pfv_encoder at 1080p (host clock, budget off / on alternating).
+
+--probe-p: the same for the p-frame size probe (pfv_enc_probe_pframe_dev: k_probe_pframe + k_pprobe_sizes), frame 1 of the synthetic streams
+behind frame 0 as an i-frame at the middle rung.  B = per rung pfv_enc_pframe_dev + pfv_enc_pack_pframe_dev to the size (payload capacity 24);
+a p-frame encode moves prev_frame, so every rung of B starts from a fresh i-frame that is enqueued OUTSIDE its event pair, and B is the sum of
+the rungs' pairs.  Sizes against trial encodes from the same prev_frame at every rung of all streams; then the host clock around pfv_encoder:
+encode_pframe with the hard budget off / on, and encode_frame against encode_pframe.
 """
 import argparse
 import ctypes
@@ -228,6 +234,126 @@ def time_budget(pkg, ctx, ladder, w=1920, h=1080, n=12, rounds=3):
             "rounds_ms": {"off": per[False], "on": per[True]}, "rungs_seen": sorted(chosen)}
 
 
+def time_probe_p(pkg, ctx, n_streams, ladder, w=1920, h=1080, warmup=3, samples=20, rounds=3):
+    lib = ctx._lib
+    fb, tb, R = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h)), len(ladder)
+    mid = R // 2
+    f0, f1 = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    sizes = ctx.alloc(n_streams * R * 4)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    probe = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full.enable_entropy()
+    upto.enable_entropy(payload_cap=24)            # every payload is "over capacity": k_ent_init / k_ent_pack return at once
+    probe.set_rung(mid)
+    probe.encode_iframe_dev(f0, coef)              # the state every measurement starts from: frame 0 as an i-frame at the middle rung
+    ev = [(ctx.event(), ctx.event()) for _ in range(R)]
+
+    def elapsed(pair):
+        ms = ctypes.c_float()
+        ctx.check(lib.pfv_event_elapsed_ms(pair[0], pair[1], ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sample_probe():
+        ctx.record(ev[0][0])
+        probe.probe_pframe_dev(f1, sizes)
+        ctx.record(ev[0][1])
+        return elapsed(ev[0])
+
+    def sample_trials(enc):
+        for r in range(R):
+            enc.set_rung(mid)
+            enc.encode_iframe_dev(f0, coef)        # outside the pair: prev_frame back to the state the probe sees
+            enc.set_rung(r)
+            ctx.record(ev[r][0])
+            enc.encode_pframe_dev(f1, mv, has, coef)
+            enc.pack_pframe_dev(mv, has, coef)
+            ctx.record(ev[r][1])
+        return sum(elapsed(p) for p in ev)
+
+    def median_ms(fn):
+        got = [fn() for _ in range(warmup + samples)]
+        return statistics.median(got[warmup:])
+    res = {"probe": [], "trials_full": [], "trials_to_size": []}
+    for _ in range(rounds):
+        res["probe"].append(median_ms(sample_probe))
+        res["trials_to_size"].append(median_ms(lambda: sample_trials(upto)))
+        res["trials_full"].append(median_ms(lambda: sample_trials(full)))
+    got = np.zeros((n_streams, R), np.uint32)
+    ctx.download(got, sizes)
+    same = True
+    for r in range(R):
+        full.set_rung(mid)
+        full.encode_iframe_dev(f0, coef)
+        full.set_rung(r)
+        full.encode_pframe_dev(f1, mv, has, coef)
+        full.pack_pframe_dev(mv, has, coef)
+        same = same and bool(np.array_equal(full.payload_sizes(), got[:, r]))
+    for a, b in ev:
+        ctx.event_destroy(a); ctx.event_destroy(b)
+    for s_ in (probe, full, upto):
+        s_.close()
+    for p in (f0, f1, coef, mv, has, sizes):
+        ctx.free(p)
+    a, b, bf = (statistics.median(res[k]) for k in ("probe", "trials_to_size", "trials_full"))
+    spread = max(res["trials_to_size"]) - min(res["trials_to_size"])
+    return {"shape": f"{n_streams} x {w}x{h}", "ladder": ladder, "samples_per_round": samples, "rounds": rounds,
+            "probe_ms": a, "trials_to_size_ms": b, "trials_full_ms": bf, "trials_to_size_spread_ms": spread,
+            "probe_over_trials_to_size": a / b if b else None, "probe_below_trials_by_more_than_spread": bool(a < b - spread),
+            "rounds_ms": res, "sizes_equal_trial_encodes": same, "bytes_stream0": [int(v) for v in got[0]]}
+
+
+def time_pframe_modes(pkg, ctx, ladder, w=1920, h=1080, n=14, rounds=3):
+    """host milliseconds per frame of one pfv_encoder behind an i-frame: encode_pframe with the soft budget, encode_pframe with the hard budget
+    (the probe on), encode_frame (automatic type, no budget)"""
+    st = pkg.SyntheticStream(w, h)
+    frs = [pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in range(n)]
+    per = {"pframe_soft": [], "pframe_hard": [], "encode_frame": []}
+    seen = {k: set() for k in per}
+    for _ in range(rounds):
+        for mode in per:
+            enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, qualities=ladder)
+            enc.set_rung(len(ladder) // 2)
+            enc.encode_iframe(frs[0])
+            budget = int(enc.probe_pframe(frs[1])[len(ladder) // 2])
+            if mode != "encode_frame":
+                enc.set_rate(budget)
+                enc.set_pframe_probe(mode == "pframe_hard")
+            secs = []
+            for fr in frs[1:]:
+                t0 = time.perf_counter()
+                kind = enc.encode_frame(fr) if mode == "encode_frame" else (enc.encode_pframe(fr), 2)[1]
+                secs.append(time.perf_counter() - t0)
+                seen[mode].add((kind, enc.rung))
+            enc.close()
+            per[mode].append(statistics.median(secs[1:]) * 1e3)
+    out = {"shape": f"1 x {w}x{h}", "ladder": ladder, "rounds_ms": per, "types_and_rungs_seen": {k: sorted(v) for k, v in seen.items()}}
+    for k, v in per.items():
+        out[k + "_ms"] = statistics.median(v)
+    return out
+
+
+def pprobe_sizes_line(pkg, ctx, w, h, kind, ladder):
+    """probed against written payload bytes of the clip's second frame as a p-frame behind its first at every rung"""
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    f0, f1 = (pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in (0, 1))
+    enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, frame_report=True, qualities=ladder)
+    probed, written = None, []
+    for r in range(len(ladder)):
+        enc.set_rung(len(ladder) // 2)
+        enc.encode_iframe(f0)
+        probed = [int(v) for v in enc.probe_pframe(f1)]
+        enc.set_rung(r)
+        enc.encode_pframe(f1)
+        written.append(enc.last_report.packet_bytes - 5)
+    enc.close()
+    return {"ladder": ladder, "width": w, "height": h, "kind": kind, "probed_bytes": probed, "written_bytes": written, "equal": probed == written}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("width", type=int)
@@ -238,6 +364,7 @@ def main():
     ap.add_argument("--qualities", default="0,2,5,10")
     ap.add_argument("--time-kernel", action="store_true")
     ap.add_argument("--probe", action="store_true")
+    ap.add_argument("--probe-p", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -255,6 +382,15 @@ def main():
                 for lad in ([0, 2, 5, 7, 10], list(range(11))):
                     print(json.dumps({"probe_timing": time_probe(pkg, ctx, n_streams, lad)}), flush=True)
             print(json.dumps({"probe_budget_latency": time_budget(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
+        if a.probe_p:
+            ladder = [int(x) for x in a.qualities.split(",") if x != ""]
+            print(json.dumps({"pprobe_sizes": pprobe_sizes_line(pkg, ctx, a.width, a.height, a.kind, ladder)}), flush=True)
+            if os.environ.get("PFV_HIP_LIB"):          # another build of the C ABI (the CPU emulator): nothing to time
+                return
+            for n_streams in (96, 1):
+                for lad in ([0, 2, 5, 7, 10], list(range(11))):
+                    print(json.dumps({"pprobe_timing": time_probe_p(pkg, ctx, n_streams, lad)}), flush=True)
+            print(json.dumps({"pprobe_encoder_latency": time_pframe_modes(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
 
 
 if __name__ == "__main__":
