@@ -170,6 +170,18 @@ class Encoder {
     }
     // byte budget per i-frame payload, 0 = off: encode_iframe takes the finest rung whose probed payload fits, the coarsest if none does
     void set_iframe_budget(uint32_t iframe_budget) { ctx_.check(pfv_encoder_set_iframe_budget(h_, iframe_budget)); }
+    // ... and the squared error per plane at every rung, sse[3 * r + plane], from the same read of the frame (pfv_encoder_probe_iframe_rd)
+    std::vector<uint32_t> probe_iframe_rd(const VideoFrame &f, std::vector<uint64_t> &sse) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        sse.assign(3 * sizes.size(), 0);
+        ctx_.check(pfv_encoder_probe_iframe_rd(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data(), sse.data()));
+        return sizes;
+    }
+    // PSNR-YUV floor per i-frame in dB, 0 = off: of the rungs within the i-frame budget that reach it the one with the fewest bytes, else the
+    // one with the smallest squared error (pfv_encoder_set_iframe_quality_floor)
+    void set_iframe_quality_floor(double min_psnr_yuv) { ctx_.check(pfv_encoder_set_iframe_quality_floor(h_, min_psnr_yuv)); }
     // payload bytes of `f` as a p-frame against the encoder's reference at every rung; nothing changes.  Error(PFV_ERR_STATE) when poisoned or finished
     std::vector<uint32_t> probe_pframe(const VideoFrame &f) const
     {

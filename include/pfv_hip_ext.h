@@ -353,6 +353,31 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
  * one-rung encoder has nothing to choose and does not probe. */
 PFV_API int pfv_encoder_set_iframe_budget(pfv_encoder *e, uint32_t iframe_budget);
 
+/* ------------------------------------------------------------------ i-frame rate-distortion probe, i-frame quality floor  [B]
+ * A finer rung does not always look better: decode indexes SCALE and q by zigzag position, encode by raster position (src/dct.rs:78-82
+ * against :92-93), so PSNR is not monotone over the ladder and a rung can cost more bytes AND more error than its coarser neighbour.  This
+ * probe measures: from ONE read of the frames, per slot of the window and EVERY rung, the payload size and counts exactly as
+ * pfv_enc_probe_iframe_dev defines them and the squared error per plane exactly as pfv_frames_sse_dev defines it between the frame and the
+ * reconstruction pfv_enc_iframe_dev at that rung would leave in prev_frame (only pixels inside the plane's w x h count).
+ *   sizes_dev  uint32[n_streams][n_rungs]; sse_dev  uint64[n_streams][n_rungs][3] (Y, U, V; undefined where the size is 0xffffffff);
+ *   stats_dev  uint32[n_streams][n_rungs][17] or NULL.
+ * Contract of pfv_enc_probe_iframe_dev: reads the tables, the window and the frame stride, changes nothing, leaves the entries of slots
+ * outside the window alone, asynchronous on the context's stream, recordable (the first call allocates the accumulators: call once before
+ * pfv_graph_begin, inside a recording it returns PFV_ERR_STATE).  Two launches, k_probe_iframe_rd + k_probe_rd_sizes
+ * (csrc/pfv_rdprobe_kernels.hip); no host-side clear, no host synchronisation. */
+PFV_API int pfv_enc_probe_iframe_rd_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev);
+PFV_API int pfv_enc_probe_iframe_rd(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out);   /* host buffers, all slots, packed; synchronises */
+PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/,
+                                        uint64_t *sse_out /*[n_rungs][3]*/);
+/* I-frame quality floor in dB of PSNR-YUV as pfv_frame_report.psnr_yuv defines it, 0 = off (default: today's behaviour, byte for byte, the
+ * i-frame budget's rule included).  On, with more than one rung: encode_iframe (and pfv_encoder_encode_frame through it) runs the
+ * rate-distortion probe in place of the size probe.  ALLOWED are the rungs that are encodable and, if an i-frame budget is set, within it;
+ * none allowed: the coarsest rung.  Of the allowed rungs with psnr_yuv >= min_psnr_yuv the one with the FEWEST bytes is taken, ties to the
+ * lower index; if none reaches the floor, the allowed rung with the smallest total squared error, ties to fewer bytes, then to the lower
+ * index.  That rung becomes the current rung.  +INFINITY is legal ("the best-looking rung that fits"); NaN and negative values return
+ * PFV_ERR_BAD_ARG.  Costs one launch pair, one download of 28 * n_rungs bytes and one synchronisation per i-frame; the frame goes up once. */
+PFV_API int pfv_encoder_set_iframe_quality_floor(pfv_encoder *e, double min_psnr_yuv);
+
 /* ------------------------------------------------------------------ p-frame size probe, hard p-frame budget, automatic frame type  [B]
  * payload bytes (the packet adds 5) that pfv_enc_pframe_dev + the entropy stage would produce for these frames against the session's CURRENT
  * prev_frame at EVERY rung, from one motion search and one forward transform of the residual: the search does not depend on the rung, only

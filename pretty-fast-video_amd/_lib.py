@@ -170,6 +170,10 @@ SIGNATURES = [
     ("pfv_enc_probe_iframe", c_int, [_P, _P, _P]),
     ("pfv_encoder_probe_iframe", c_int, [_P, _P, _P, _P, _P]),
     ("pfv_encoder_set_iframe_budget", c_int, [_P, ctypes.c_uint32]),
+    ("pfv_enc_probe_iframe_rd_dev", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_iframe_rd", c_int, [_P, _P, _P, _P]),
+    ("pfv_encoder_probe_iframe_rd", c_int, [_P, _P, _P, _P, _P, _P]),
+    ("pfv_encoder_set_iframe_quality_floor", c_int, [_P, ctypes.c_double]),
     ("pfv_enc_probe_pframe_dev", c_int, [_P, _P, _P, _P]),
     ("pfv_enc_probe_pframe", c_int, [_P, _P, _P]),
     ("pfv_encoder_probe_pframe", c_int, [_P, _P, _P, _P, _P]),

@@ -16,6 +16,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #include "pfv_quality_kernels.hip"
 #include "pfv_entropy_kernels.hip"
 #include "pfv_probe_kernels.hip"
+#include "pfv_rdprobe_kernels.hip"
 #include "pfv_pprobe_kernels.hip"
 #include "pfv_entdec_kernels.hip"
 #include "pfv_synth_kernels.hip"
@@ -71,6 +72,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_sessions.hip"
 #include "pfv_quality.hip"
 #include "pfv_probe.hip"
+#include "pfv_rdprobe.hip"
 #include "pfv_pprobe.hip"
 #include "pfv_container.hip"
 #include "pfv_stream_objects.hip"

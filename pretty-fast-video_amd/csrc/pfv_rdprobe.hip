@@ -1,0 +1,95 @@
+// pfv_rdprobe.hip -- the i-frame rate-distortion probe of an encoder session (pfv_enc_probe_iframe_rd*): payload bytes and squared error per
+// plane of the window's frames as i-frames at every rung of the ladder, from one read of the frames.  Kernels: pfv_rdprobe_kernels.hip.
+// Part of the one translation unit of the C ABI: included by pfv_capi.hip behind pfv_probe.hip, never compiled on its own.
+
+// the kernels' accumulators: the size probe's rows (probe_acc) and the plane sums [n_streams][n_rungs][3]; made and cleared by the first
+// call, left clear by every k_probe_rd_sizes
+static int rd_probe_acc(pfv_enc_session *s)
+{
+    pfv_ctx *ctx = s->ctx;
+    if (ctx->capturing && (!s->probe_acc || !s->rd_acc))
+        return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd_dev: the accumulator needs an allocation, which a graph recording cannot hold -- call once before pfv_graph_begin");
+    int rc = probe_acc(s);
+    if (rc || s->rd_acc) return rc;
+    const size_t bytes = (size_t)s->n_streams * (size_t)s->n_rungs * 3 * sizeof(uint64_t);
+    HIP_TRY(ctx, hipMalloc((void **)&s->rd_acc, bytes));
+    hipError_t e = hipMemsetAsync(s->rd_acc, 0, bytes, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(s->rd_acc);
+        s->rd_acc = nullptr;
+        return hip_fail(ctx, e, "pfv_enc_probe_iframe_rd_dev");
+    }
+    return PFV_OK;
+}
+
+// slots [win_first, win_first + win_count), as probe_launch
+static int rd_probe_launch(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev)
+{
+    pfv_ctx *ctx = s->ctx;
+    int rc = rd_probe_acc(s);
+    if (rc) return rc;
+    const size_t first = (size_t)s->win_first, R = (size_t)s->n_rungs;
+    const size_t stride = s->in_stride ? s->in_stride : (size_t)s->geom.src_frame_bytes;
+    const uint8_t *src = frames_dev + first * stride;
+    const FrameGeom g = enc_win_geom(s, s->win_count, src);
+    uint32_t *acc = s->probe_acc + first * R * kProbeAcc;
+    unsigned long long *sse_acc = (unsigned long long *)s->rd_acc + first * R * 3;
+    const QTab *qt = (const QTab *)s->qtab_dev;
+    if (use_small_grid(s->lane_mapping, g)) {
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+    } else {
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+    }
+    hipLaunchKernelGGL(k_probe_rd_sizes, dim3((unsigned)((size_t)s->win_count * R)), dim3(64), 0, ctx->stream, acc, sizes_dev + first * R,
+                       stats_dev ? stats_dev + first * R * kProbeStats : (uint32_t *)nullptr, sse_acc, (unsigned long long *)sse_dev + first * R * 3);
+    return launch_check(ctx, "k_probe_iframe_rd / k_probe_rd_sizes");
+}
+
+extern "C" {
+
+PFV_API int pfv_enc_probe_iframe_rd_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    pfv_ctx *ctx = s->ctx;
+    if (!frames_dev || !sizes_dev || !sse_dev) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_iframe_rd_dev: null buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return rd_probe_launch(s, frames_dev, sizes_dev, sse_dev, stats_dev);
+}
+
+}  // extern "C"
+// the frames in the session's staging (all slots, packed) -> sizes_out [n_streams][n_rungs], sse_out [n_streams][n_rungs][3]; one download
+// of 28 bytes per (stream, rung) -- the sums first, so that both parts stay aligned -- and one synchronisation
+static int rd_probe_staged(pfv_enc_session *s, uint32_t *sizes_out, uint64_t *sse_out)
+{
+    pfv_ctx *ctx = s->ctx;
+    const size_t n = (size_t)s->n_streams * (size_t)s->n_rungs;
+    const size_t sse_bytes = n * 3 * sizeof(uint64_t), bytes = sse_bytes + n * sizeof(uint32_t);
+    if (!s->rd_out) HIP_TRY(ctx, hipMalloc((void **)&s->rd_out, bytes));
+    std::vector<uint8_t> host(bytes);
+    int rc = rd_probe_launch(s, s->st_frames, (uint32_t *)((uint8_t *)s->rd_out + sse_bytes), s->rd_out, nullptr);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), s->rd_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(sse_out, host.data(), sse_bytes);
+    memcpy(sizes_out, host.data() + sse_bytes, n * sizeof(uint32_t));
+    return PFV_OK;
+}
+extern "C" {
+
+PFV_API int pfv_enc_probe_iframe_rd(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    pfv_ctx *ctx = s->ctx;
+    if (!frames || !sizes_out || !sse_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_iframe_rd: null buffer");
+    if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd: the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
+    if (ctx->capturing) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd: host-pointer entry points cannot be recorded");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = enc_staging(s);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams, hipMemcpyHostToDevice, ctx->stream));
+    return rd_probe_staged(s, sizes_out, sse_out);
+}
+
+}  // extern "C"

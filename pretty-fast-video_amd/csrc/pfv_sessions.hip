@@ -108,6 +108,10 @@ struct pfv_enc_session {
     // i-frame size probe (pfv_probe.hip): the kernels' accumulator [n_streams][n_rungs][kProbeAcc], zero between calls; sizes of the host-buffer form
     uint32_t *probe_acc = nullptr;
     uint32_t *probe_sizes = nullptr;
+    // i-frame rate-distortion probe (pfv_rdprobe.hip): the plane sums' accumulator [n_streams][n_rungs][3], zero between calls (the sizes use
+    // probe_acc); sums [n_streams][n_rungs][3] with the sizes [n_streams][n_rungs] behind them of the host-buffer form
+    uint64_t *rd_acc = nullptr;
+    uint64_t *rd_out = nullptr;
     // p-frame size probe (pfv_pprobe.hip): accumulator [n_streams][n_rungs][kPProbeAcc], zero between calls, with min_err of every rung behind it;
     // sizes [n_streams][n_rungs] and counts [n_streams][n_rungs][kPProbeStats] of the host-buffer form
     uint32_t *pprobe_acc = nullptr;
@@ -231,7 +235,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->pprobe_acc, s->pprobe_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)

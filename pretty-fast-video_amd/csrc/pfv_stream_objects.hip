@@ -79,6 +79,7 @@ struct pfv_encoder {
     int last_rung = -1;                    // rung of the last frame written (-1: none yet)
     uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
     uint32_t budget_i = 0;                 // i-frame payload bytes (pfv_encoder_set_iframe_budget); 0: off
+    double floor_i = 0.0;                  // i-frame PSNR-YUV floor in dB (pfv_encoder_set_iframe_quality_floor); 0: off
     // p-frame size probe (pfv_encoder_set_pframe_probe): the hard p-frame budget; automatic frame types (pfv_encoder_encode_frame)
     bool pprobe_on = false;
     int gop_max = 0;                       // pfv_encoder_set_gop: an i-frame is forced once this many frames have followed the last one; 0: never
@@ -556,6 +557,15 @@ PFV_API int pfv_encoder_set_iframe_budget(pfv_encoder *e, uint32_t iframe_budget
     return PFV_OK;
 }
 
+// i-frame quality floor in dB of PSNR-YUV, 0 = off; the rule is at the declaration (include/pfv_hip_ext.h) and in floor_rung
+PFV_API int pfv_encoder_set_iframe_quality_floor(pfv_encoder *e, double min_psnr_yuv)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!(min_psnr_yuv >= 0.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_iframe_quality_floor: the floor must be >= 0 dB (+INFINITY is legal, NaN is not)");
+    e->floor_i = min_psnr_yuv;
+    return PFV_OK;
+}
+
 // the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
 static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
 {
@@ -688,8 +698,26 @@ static int budget_rung(const pfv_enc_session *s, const uint32_t *sizes, uint32_t
         if (sizes[r] != kEntErrOversize && sizes[r] <= budget) return r;
     return s->n_rungs - 1;
 }
+// The i-frame quality floor's rung from the probed sizes and plane sums [n_rungs][3].  Allowed: encodable and, under an i-frame budget, within
+// it.  Of the allowed rungs whose PSNR-YUV (pfv_frame_report's) reaches the floor the one with the fewest bytes; if none does, the allowed rung
+// with the smallest squared error, then the fewest bytes; ties to the lower index.  No rung allowed: the coarsest, as budget_rung.
+static int floor_rung(const pfv_encoder *e, const uint32_t *sizes, const uint64_t *sse)
+{
+    const pfv_enc_session *s = e->hot;
+    const uint64_t samples = (uint64_t)pfv_frame_bytes(e->width, e->height);
+    int meets = -1, best = -1;
+    uint64_t best_sse = 0;
+    for (int r = 0; r < s->n_rungs; r++) {
+        if (sizes[r] == kEntErrOversize || (e->budget_i && sizes[r] > e->budget_i)) continue;
+        const uint64_t total = sse[3 * r] + sse[3 * r + 1] + sse[3 * r + 2];
+        if (pfv_psnr(total, samples) >= e->floor_i && (meets < 0 || sizes[r] < sizes[meets])) meets = r;
+        if (best < 0 || total < best_sse || (total == best_sse && sizes[r] < sizes[best])) { best = r; best_sse = total; }
+    }
+    return meets >= 0 ? meets : best >= 0 ? best : s->n_rungs - 1;
+}
 // The i-frame byte budget: the frame goes up into the session's staging, the probe sizes it at every rung, and the finest rung whose payload
-// fits becomes the current rung (the coarsest if none does; a rung the probe marks not encodable does not fit).
+// fits becomes the current rung (the coarsest if none does; a rung the probe marks not encodable does not fit).  With a quality floor the
+// rate-distortion probe runs in its place and floor_rung chooses.
 // staged: the frame lies in the session's staging already; probed: ... and these are its i-frame sizes (pfv_encoder_encode_frame)
 static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged, const uint32_t *probed)
 {
@@ -698,6 +726,13 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
     int rc = enc_staging(s);
     if (!rc && !staged) rc = upload_planes(e, y, u, v);
     uint32_t sizes[kMaxRungs];
+    if (e->floor_i > 0.0) {
+        uint64_t sse[kMaxRungs][3];
+        if (!rc) rc = rd_probe_staged(s, sizes, &sse[0][0]);
+        if (rc) return rc;
+        s->rung = floor_rung(e, sizes, &sse[0][0]);
+        return PFV_OK;
+    }
     if (!rc && !probed) rc = probe_staged(s, sizes);
     if (rc) return rc;
     s->rung = budget_rung(s, probed ? probed : sizes, e->budget_i);
@@ -708,7 +743,7 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
 static int write_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false, const uint32_t *probed = nullptr)
 {
     int rc;
-    const bool budget = e->budget_i != 0 && e->hot->n_rungs > 1;   // one rung: nothing to choose
+    const bool budget = (e->budget_i != 0 || e->floor_i > 0.0) && e->hot->n_rungs > 1;   // one rung: nothing to choose
     if (budget && (rc = choose_iframe_rung(e, y, u, v, staged, probed))) return rc;
     staged = staged || budget;
     if (e->device_entropy) return encode_on_device(e, false, staged);      // an i-frame replaces prev_frame entirely: clears a poisoned state
@@ -742,6 +777,17 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
     if (!rc) rc = probe_staged(e->hot, sizes_out);
+    return rc;
+}
+// ... and its squared error per plane at every rung [n_rungs][3], from the same read of the frame
+PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!y || !u || !v || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_rd: null buffer");
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    int rc = enc_staging(e->hot);
+    if (!rc) rc = upload_planes(e, y, u, v);
+    if (!rc) rc = rd_probe_staged(e->hot, sizes_out, sse_out);
     return rc;
 }
 // the frame up into the session's staging and sized as a p-frame at every rung (counts: [n_rungs][kPProbeStats], or nullptr)

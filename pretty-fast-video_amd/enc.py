@@ -16,10 +16,10 @@ from .frame import VideoFrame
 
 class Encoder:
     def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
-                 frame_report: bool = False, qualities=None, iframe_budget: int = 0):
+                 frame_report: bool = False, qualities=None, iframe_budget: int = 0, iframe_quality_floor: float = 0.0):
         """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
         quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame.  ``iframe_budget``: see
-        ``set_iframe_budget``"""
+        ``set_iframe_budget``; ``iframe_quality_floor``: see ``set_iframe_quality_floor``"""
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
         h = ctypes.c_void_p()
@@ -38,6 +38,8 @@ class Encoder:
             ctx.check(ctx._lib.pfv_encoder_set_frame_report(h, 1))
         if iframe_budget:
             ctx.check(ctx._lib.pfv_encoder_set_iframe_budget(h, int(iframe_budget)))
+        if iframe_quality_floor:
+            ctx.check(ctx._lib.pfv_encoder_set_iframe_quality_floor(h, float(iframe_quality_floor)))
         self.finished = False
         ctx._sessions.add(self)
         self._flush()                                               # header (src/enc.rs:70)
@@ -106,6 +108,22 @@ class Encoder:
         self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
                                                               ptr(frame.plane_v.pixels), ptr(sizes)))
         return sizes
+
+    def set_iframe_quality_floor(self, min_psnr_yuv: float = 0.0):
+        """PSNR-YUV floor in dB per i-frame (0: off; inf: the best-looking rung that fits): encode_iframe probes size and squared error at
+        every rung and takes, of the rungs within the i-frame budget that reach the floor, the one with the fewest bytes -- if none does,
+        the one with the smallest error; that rung becomes the current rung (pfv_encoder_set_iframe_quality_floor)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_iframe_quality_floor(self.handle, float(min_psnr_yuv)))
+
+    def probe_iframe_rd(self, frame: VideoFrame):
+        """(sizes uint32 [n_rungs], sse uint64 [n_rungs, 3]) of `frame` as an i-frame at every rung: payload bytes as probe_iframe and the
+        squared error per plane a frame report would show at that rung; the stream, the encoder's reference and the rung stay as they are"""
+        import numpy as np
+        self._check_frame(frame)
+        sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe_rd(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
+                                                                 ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse)))
+        return sizes, sse
 
     def probe_pframe(self, frame: VideoFrame):
         """payload bytes of `frame` as a p-frame against the encoder's reference at every rung, uint32 [n_rungs] (0xffffffff: not encodable at

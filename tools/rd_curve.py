@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -25,6 +25,12 @@ behind frame 0 as an i-frame at the middle rung.  B = per rung pfv_enc_pframe_de
 a p-frame encode moves prev_frame, so every rung of B starts from a fresh i-frame that is enqueued OUTSIDE its event pair, and B is the sum of
 the rungs' pairs.  Sizes against trial encodes from the same prev_frame at every rung of all streams; then the host clock around pfv_encoder:
 encode_pframe with the hard budget off / on, and encode_frame against encode_pframe.
+
+--probe-rd: the i-frame rate-distortion probe (pfv_encoder_probe_iframe_rd) on the clip's first frame -- probed against written payload bytes
+and probed against reported squared error per rung -- and then its timing at 96 x 1080p, ladders 0,2,5,7,10 and 0..10, by --probe's method:
+A = the probe's two launches (k_probe_iframe_rd + k_probe_rd_sizes); B = the way to the same numbers without it, per rung
+pfv_enc_session_set_rung + pfv_enc_iframe_dev + the entropy stage to the size + pfv_enc_distortion_dev; C = pfv_enc_probe_iframe_dev alone
+(what the distortion half adds is A - C).  The answers are compared rung by rung over all streams.
 """
 import argparse
 import ctypes
@@ -208,6 +214,91 @@ def time_probe(pkg, ctx, n_streams, ladder, w=1920, h=1080, warmup=3, samples=20
             "rounds_ms": res, "sizes_equal_trial_encodes": same, "bytes_stream0": [int(v) for v in got[0]]}
 
 
+def probe_rd_line(pkg, ctx, w, h, kind, ladder):
+    """probed against written payload bytes and probed against reported squared error of the clip's first frame at every rung"""
+    fr = pkg.VideoFrame.from_packed(w, h, pkg.SyntheticStream(w, h, kind=kind).frame(0))
+    enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, frame_report=True, qualities=ladder)
+    sizes, sse = enc.probe_iframe_rd(fr)
+    probed, probed_sse = [int(v) for v in sizes], [[int(v) for v in row] for row in sse]
+    written, reported, psnr = [], [], []
+    for r in range(len(ladder)):
+        enc.set_rung(r)
+        enc.encode_iframe(fr)
+        rep = enc.last_report
+        written.append(rep.packet_bytes - 5)
+        reported.append([int(v) for v in rep.sse])
+        psnr.append(rep.psnr_yuv)
+    enc.close()
+    return {"ladder": ladder, "width": w, "height": h, "kind": kind, "probed_bytes": probed, "written_bytes": written, "probed_sse": probed_sse,
+            "reported_sse": reported, "psnr_yuv": psnr, "equal": probed == written and probed_sse == reported}
+
+
+def time_probe_rd(pkg, ctx, n_streams, ladder, w=1920, h=1080, warmup=3, samples=20, rounds=3):
+    lib = ctx._lib
+    fb, tb, R = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h)), len(ladder)
+    frames, coef = ctx.alloc(fb * n_streams), ctx.alloc(n_streams * tb * 512)
+    sizes, sse, sse_b = ctx.alloc(n_streams * R * 4), ctx.alloc(n_streams * R * 24), ctx.alloc(n_streams * 24)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, frames)
+    probe = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto.enable_entropy(payload_cap=24)            # the stage "up to the size", as time_probe
+    e0, e1 = ctx.event(), ctx.event()
+
+    def trial():
+        for r in range(R):
+            upto.set_rung(r)
+            upto.encode_iframe_dev(frames, coef)
+            upto.pack_iframe_dev(coef)
+            upto.distortion_dev(frames, sse_b)
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got)
+    res = {"rd_probe": [], "trials": [], "size_probe": []}
+    for _ in range(rounds):
+        res["rd_probe"].append(median_ms(lambda: probe.probe_iframe_rd_dev(frames, sizes, sse)))
+        res["trials"].append(median_ms(trial))
+        res["size_probe"].append(median_ms(lambda: probe.probe_iframe_dev(frames, sizes)))
+    # the answers: the probe's against the trial encodes' (rung by rung, all streams)
+    probe.probe_iframe_rd_dev(frames, sizes, sse)
+    got, got_sse = np.zeros((n_streams, R), np.uint32), np.zeros((n_streams, R, 3), np.uint64)
+    ctx.download(got, sizes)
+    ctx.download(got_sse, sse)
+    full = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full.enable_entropy()
+    same_sizes, same_sse = [], []
+    one = np.zeros((n_streams, 3), np.uint64)
+    for r in range(R):
+        full.set_rung(r)
+        full.encode_iframe_dev(frames, coef)
+        full.pack_iframe_dev(coef)
+        full.distortion_dev(frames, sse_b)
+        same_sizes.append(bool(np.array_equal(full.payload_sizes(), got[:, r])))
+        ctx.download(one, sse_b)
+        same_sse.append(bool(np.array_equal(one, got_sse[:, r])))
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    for s in (probe, upto, full):
+        s.close()
+    for p in (frames, coef, sizes, sse, sse_b):
+        ctx.free(p)
+    a, b, c = (statistics.median(res[k]) for k in ("rd_probe", "trials", "size_probe"))
+    spread = {k: max(v) - min(v) for k, v in res.items()}
+    samples_n = n_streams * fb
+    return {"shape": f"{n_streams} x {w}x{h}", "ladder": ladder, "samples_per_round": samples, "rounds": rounds,
+            "A_rd_probe_ms": a, "B_trials_ms": b, "C_size_probe_ms": c, "spread_ms": spread, "A_over_B": a / b if b else None,
+            "A_below_B_by_more_than_Bs_spread": bool(a < b - spread["trials"]), "distortion_half_ms": a - c, "rounds_ms": res,
+            "sizes_equal_per_rung": same_sizes, "sse_equal_per_rung": same_sse, "bytes_stream0": [int(v) for v in got[0]],
+            "psnr_yuv_all_streams": [pkg.psnr(int(got_sse[:, r].sum()), samples_n) for r in range(R)]}
+
+
 def time_budget(pkg, ctx, ladder, w=1920, h=1080, n=12, rounds=3):
     """host milliseconds per encode_iframe of one pfv_encoder, i-frame budget off / on (a budget the middle rung meets)"""
     st = pkg.SyntheticStream(w, h)
@@ -365,6 +456,7 @@ def main():
     ap.add_argument("--time-kernel", action="store_true")
     ap.add_argument("--probe", action="store_true")
     ap.add_argument("--probe-p", action="store_true")
+    ap.add_argument("--probe-rd", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -391,6 +483,13 @@ def main():
                 for lad in ([0, 2, 5, 7, 10], list(range(11))):
                     print(json.dumps({"pprobe_timing": time_probe_p(pkg, ctx, n_streams, lad)}), flush=True)
             print(json.dumps({"pprobe_encoder_latency": time_pframe_modes(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
+        if a.probe_rd:
+            ladder = [int(x) for x in a.qualities.split(",") if x != ""]
+            print(json.dumps({"probe_rd": probe_rd_line(pkg, ctx, a.width, a.height, a.kind, ladder)}), flush=True)
+            if os.environ.get("PFV_HIP_LIB"):          # another build of the C ABI (the CPU emulator): nothing to time
+                return
+            for lad in ([0, 2, 5, 7, 10], list(range(11))):
+                print(json.dumps({"probe_rd_timing": time_probe_rd(pkg, ctx, 96, lad)}), flush=True)
 
 
 if __name__ == "__main__":
