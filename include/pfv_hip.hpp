@@ -190,6 +190,19 @@ class Encoder {
         ctx_.check(pfv_encoder_probe_pframe(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data()));
         return sizes;
     }
+    // ... and the squared error per plane at every rung, sse[3 * r + plane], from the same search and transform (pfv_encoder_probe_pframe_rd)
+    std::vector<uint32_t> probe_pframe_rd(const VideoFrame &f, std::vector<uint64_t> &sse) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        sse.assign(3 * sizes.size(), 0);
+        ctx_.check(pfv_encoder_probe_pframe_rd(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data(), sse.data()));
+        return sizes;
+    }
+    // PSNR-YUV floor per p-frame in dB, 0 = off: of the rungs within the set_rate budget (a hard cap here) that reach it the one with the fewest
+    // bytes, else the one with the smallest squared error; encode_frame then weighs the p-frame against the i-frame by the same measure
+    // (pfv_encoder_set_pframe_quality_floor)
+    void set_pframe_quality_floor(double min_psnr_yuv) { ctx_.check(pfv_encoder_set_pframe_quality_floor(h_, min_psnr_yuv)); }
     // on, with a set_rate budget and more than one rung: encode_pframe takes the finest rung whose probed payload fits, the coarsest if none does
     void set_pframe_probe(bool on) { ctx_.check(pfv_encoder_set_pframe_probe(h_, on ? 1 : 0)); }
     // encode_frame forces an i-frame once max_interval frames (drop frames included) have followed the last one; 0 = never

@@ -412,9 +412,43 @@ PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on);
  * Costs per frame behind the first: up to two launch pairs, two downloads of at most 84 * n_rungs and 4 * n_rungs bytes, each with its
  * synchronisation, before the encode itself.  Rule 4 means what it says and is NOT a scene-cut detector: residuals are halved
  * (src/common.rs:118-119, :304), so a p-frame across a cut is often the smaller one (texture, noise) and is then written.  Frame reports
- * work as for the explicit calls.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have none of this. */
+ * work as for the explicit calls.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have none of this.
+ *   4 with the p-frame quality floor on (pfv_encoder_set_pframe_quality_floor, below; rules 1 to 3 stay, rp = the floor's rung): the frame is
+ *      measured as an i-frame by the rate-distortion probe from the same upload; ri = the rung encode_iframe would choose with its own budget and
+ *      floor settings, from these results (no second probe, no second upload).  The candidates are the p-frame at rp and the i-frame at ri; each
+ *      MEETS when its PSNR-YUV is at or above the P-FRAME floor.  Exactly one meets: that one.  Both meet: the one with fewer bytes, ties to the
+ *      i-frame (today's <=).  Neither meets: the smaller total squared error, ties to fewer bytes, then to the i-frame.  A candidate that is
+ *      not encodable never meets and loses to one that is.  The i-frame is written at ri, the p-frame at rp; either becomes the current rung. */
 PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval);
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out /* 1 i, 2 p, 3 drop */);
+
+/* ------------------------------------------------------------------ p-frame rate-distortion probe, p-frame quality floor  [B]
+ * A p-frame is often the smaller frame AND the worse-looking one: residuals are halved, and a skipped macroblock costs no bytes whatever its
+ * error.  This probe measures: from ONE motion search and ONE forward transform of the residual, per slot of the window and EVERY rung, the
+ * payload size and counts exactly as pfv_enc_probe_pframe_dev defines them and the squared error per plane exactly as pfv_frames_sse_dev
+ * defines it between the frame and the reconstruction pfv_enc_pframe_dev at that rung would leave in prev_frame (only pixels inside the
+ * plane's w x h count; a skipped macroblock reconstructs to its patch).
+ *   sizes_dev  uint32[n_streams][n_rungs]; sse_dev  uint64[n_streams][n_rungs][3] (Y, U, V; undefined where the size is 0xffffffff);
+ *   stats_dev  uint32[n_streams][n_rungs][PFV_PPROBE_STATS] or NULL.
+ * Contract of pfv_enc_probe_pframe_dev: reads the tables, the window, the frame stride and prev_frame, changes nothing (prev_frame, the
+ * ping-pong index and the current rung stay as they are), leaves the entries of slots outside the window alone, asynchronous on the context's
+ * stream, recordable (the first call allocates the accumulators: call once before pfv_graph_begin, inside a recording it returns
+ * PFV_ERR_STATE).  Two launches, k_probe_pframe_rd + k_pprobe_rd_sizes (csrc/pfv_prdprobe_kernels.hip); no host-side clear, no host
+ * synchronisation.  One lane mapping, 8 lanes per macroblock. */
+PFV_API int pfv_enc_probe_pframe_rd_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev);
+PFV_API int pfv_enc_probe_pframe_rd(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out);   /* host buffers, all slots, packed; synchronises */
+/* pfv_encoder: the same against the encoder's reference; no state changes.  PFV_ERR_STATE when the encoder is poisoned or finished. */
+PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/,
+                                        uint64_t *sse_out /*[n_rungs][3]*/);
+/* P-frame quality floor in dB of PSNR-YUV as pfv_frame_report.psnr_yuv defines it, 0 = off (default: today's behaviour, byte for byte).  On,
+ * with more than one rung: encode_pframe runs the rate-distortion probe and chooses by the i-frame floor's rule.  ALLOWED are the rungs that
+ * are encodable and, if a pfv_encoder_set_rate budget is set, within it -- with the floor on that budget is a hard cap whether or not
+ * pfv_encoder_set_pframe_probe is on, and the soft rule is not applied; none allowed: the coarsest rung.  Of the allowed rungs with
+ * psnr_yuv >= min_psnr_yuv the one with the FEWEST bytes is taken, ties to the lower index; if none reaches the floor, the allowed rung with
+ * the smallest total squared error, ties to fewer bytes, then to the lower index.  That rung becomes the current rung.  +INFINITY is legal;
+ * NaN and negative values return PFV_ERR_BAD_ARG.  pfv_encoder_encode_frame: rule 4 above changes with the floor on.  Costs one launch pair,
+ * one download of 28 * n_rungs bytes and one synchronisation per p-frame; the frame goes up once. */
+PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr_yuv);
 
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);

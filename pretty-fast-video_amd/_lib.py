@@ -177,6 +177,10 @@ SIGNATURES = [
     ("pfv_enc_probe_pframe_dev", c_int, [_P, _P, _P, _P]),
     ("pfv_enc_probe_pframe", c_int, [_P, _P, _P]),
     ("pfv_encoder_probe_pframe", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_pframe_rd_dev", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_pframe_rd", c_int, [_P, _P, _P, _P]),
+    ("pfv_encoder_probe_pframe_rd", c_int, [_P, _P, _P, _P, _P, _P]),
+    ("pfv_encoder_set_pframe_quality_floor", c_int, [_P, ctypes.c_double]),
     ("pfv_encoder_set_pframe_probe", c_int, [_P, c_int]),
     ("pfv_encoder_set_gop", c_int, [_P, c_int]),
     ("pfv_encoder_encode_frame", c_int, [_P, _P, _P, _P, _P]),

@@ -2,24 +2,31 @@
 // plane of the window's frames as i-frames at every rung of the ladder, from one read of the frames.  Kernels: pfv_rdprobe_kernels.hip.
 // Part of the one translation unit of the C ABI: included by pfv_capi.hip behind pfv_probe.hip, never compiled on its own.
 
-// the kernels' accumulators: the size probe's rows (probe_acc) and the plane sums [n_streams][n_rungs][3]; made and cleared by the first
-// call, left clear by every k_probe_rd_sizes
-static int rd_probe_acc(pfv_enc_session *s)
+// the plane sums' accumulator [n_streams][n_rungs][3], shared by both rate-distortion probes (calls are ordered on the context's stream): made and
+// cleared by the first call, left clear by every k_probe_rd_sizes / k_pprobe_rd_sizes
+static int rd_sums_acc(pfv_enc_session *s, const char *who)
 {
     pfv_ctx *ctx = s->ctx;
-    if (ctx->capturing && (!s->probe_acc || !s->rd_acc))
-        return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd_dev: the accumulator needs an allocation, which a graph recording cannot hold -- call once before pfv_graph_begin");
-    int rc = probe_acc(s);
-    if (rc || s->rd_acc) return rc;
+    if (s->rd_acc) return PFV_OK;
     const size_t bytes = (size_t)s->n_streams * (size_t)s->n_rungs * 3 * sizeof(uint64_t);
     HIP_TRY(ctx, hipMalloc((void **)&s->rd_acc, bytes));
     hipError_t e = hipMemsetAsync(s->rd_acc, 0, bytes, ctx->stream);
     if (e != hipSuccess) {
         (void)hipFree(s->rd_acc);
         s->rd_acc = nullptr;
-        return hip_fail(ctx, e, "pfv_enc_probe_iframe_rd_dev");
+        return hip_fail(ctx, e, who);
     }
     return PFV_OK;
+}
+// the kernels' accumulators: the size probe's rows (probe_acc) and the plane sums
+static int rd_probe_acc(pfv_enc_session *s)
+{
+    pfv_ctx *ctx = s->ctx;
+    if (ctx->capturing && (!s->probe_acc || !s->rd_acc))
+        return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd_dev: the accumulator needs an allocation, which a graph recording cannot hold -- call once before pfv_graph_begin");
+    int rc = probe_acc(s);
+    if (!rc) rc = rd_sums_acc(s, "pfv_enc_probe_iframe_rd_dev");
+    return rc;
 }
 
 // slots [win_first, win_first + win_count), as probe_launch

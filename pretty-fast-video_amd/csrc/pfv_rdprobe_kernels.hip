@@ -44,9 +44,11 @@ __device__ __forceinline__ uint4 rd_picture_mask(const PlaneGeom &p, int x, int 
 }
 
 // The closed loop's second half for one half-macroblock at one rung: nn = the lane's scaled coefficients (column layout), rc / dq = the rung's
-// reciprocals and dequantiser products [64] (LDS; dq holds f32 bits in the float form) -> the 16 reconstructed pixels of the lane's row
-template <bool FLT>
-__device__ __forceinline__ uint4 rd_recon_row(const f2 (&nn)[8], const float *rc, const int *dq, int *xw, int slot, int i)
+// reciprocals and dequantiser products [64] (LDS; dq holds f32 bits in the float form) -> the 16 reconstructed pixels of the lane's row.
+// RESIDUAL (the p-frame probe, pfv_prdprobe_kernels.hip): nn is a residual's and `pred` the lane's row of the prediction -- the tail is
+// penc_half's apply_residuals (src/common.rs:98-104), pred + 2 * min(t, 127), saturated, in place of the pixel clamp.
+template <bool FLT, bool RESIDUAL = false>
+__device__ __forceinline__ uint4 rd_recon_row(const f2 (&nn)[8], const float *rc, const int *dq, int *xw, int slot, int i, const uint4 &pred = uint4())
 {
     int *mb = xw + slot * kMBPitch;
     if (FLT) {   // inverse_half_f<true> behind quant_div
@@ -56,6 +58,16 @@ __device__ __forceinline__ uint4 rd_recon_row(const f2 (&nn)[8], const float *rc
         fidct8(c);   // dct_inverse_transform_columns
         f_cols_to_rows(c, mb, i, slot & 3);
         fidct8(c);   // dct_inverse_transform_rows
+        if (RESIDUAL) {   // inverse_half_f<false>'s v >> 8, then apply_residuals
+            f2 pp[8];
+            unpack_row_f(pred, pp);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const f2 t = f2floor(c[k] * f2s(1.0f / 256.0f));
+                c[k] = pp[k] + f2{__builtin_fminf(t[0], 127.0f), __builtin_fminf(t[1], 127.0f)} * f2s(2.0f);
+            }
+            return pack_row_f(c);
+        }
 #pragma unroll
         for (int k = 0; k < 8; k++) c[k] = iframe_pixel_f(c[k]);
         return pack_row_f(c);
@@ -71,16 +83,19 @@ __device__ __forceinline__ uint4 rd_recon_row(const f2 (&nn)[8], const float *rc
     idct8(v[0]);
     idct8(v[1]);
     cols_to_rows2(v, mb, i, slot & 3);
+    int pp[2][8];
+    if (RESIDUAL) unpack_row(pred, pp);
 #pragma unroll
     for (int s = 0; s < 2; s++) {
         idct8(v[s]);
 #pragma unroll
-        for (int k = 0; k < 8; k++) v[s][k] = min(max((v[s][k] >> 8) + 128, 0), 255);
+        for (int k = 0; k < 8; k++)
+            v[s][k] = RESIDUAL ? min(max(pp[s][k] + 2 * min(v[s][k] >> 8, 127), 0), 255) : min(max((v[s][k] >> 8) + 128, 0), 255);
     }
     return pack_row(v);
 }
 
-// The distortion half of the rung loop (k_probe_iframe_rd; a p-frame probe could run it on residuals): a = the lane's source rows with the
+// The distortion half of the rung loop (k_probe_iframe_rd; k_probe_pframe_rd has its own, on residuals and with a skip test per rung): a = the lane's source rows with the
 // pixels outside the picture zeroed, mask = those pixels' byte masks, rcp / deq = the constants of all rungs [n_rungs][64] (LDS), sums = the
 // 64-bit sum of the wavefront's (stream, plane) at rung 0, PITCH words per rung.
 template <bool FLT, int LPM, int PITCH>

@@ -116,6 +116,9 @@ struct pfv_enc_session {
     // sizes [n_streams][n_rungs] and counts [n_streams][n_rungs][kPProbeStats] of the host-buffer form
     uint32_t *pprobe_acc = nullptr;
     uint32_t *pprobe_out = nullptr;
+    // p-frame rate-distortion probe (pfv_prdprobe.hip): pprobe_acc and rd_acc are its accumulators; of the host-buffer form the sums
+    // [n_streams][n_rungs][3], the sizes [n_streams][n_rungs] and the counts [n_streams][n_rungs][kPProbeStats], in this order
+    uint64_t *prd_out = nullptr;
     // device entropy stage (pfv_enc_entropy_enable)
     bool ent_on = false;
     uint32_t ent_cap = 0;
@@ -235,7 +238,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)

@@ -80,6 +80,7 @@ struct pfv_encoder {
     uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
     uint32_t budget_i = 0;                 // i-frame payload bytes (pfv_encoder_set_iframe_budget); 0: off
     double floor_i = 0.0;                  // i-frame PSNR-YUV floor in dB (pfv_encoder_set_iframe_quality_floor); 0: off
+    double floor_p = 0.0;                  // p-frame PSNR-YUV floor in dB (pfv_encoder_set_pframe_quality_floor); 0: off
     // p-frame size probe (pfv_encoder_set_pframe_probe): the hard p-frame budget; automatic frame types (pfv_encoder_encode_frame)
     bool pprobe_on = false;
     int gop_max = 0;                       // pfv_encoder_set_gop: an i-frame is forced once this many frames have followed the last one; 0: never
@@ -566,6 +567,18 @@ PFV_API int pfv_encoder_set_iframe_quality_floor(pfv_encoder *e, double min_psnr
     return PFV_OK;
 }
 
+// p-frame quality floor in dB of PSNR-YUV, 0 = off; the rules are at the declaration (include/pfv_hip_ext.h), in floor_rung and in
+// pfv_encoder_encode_frame
+PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr_yuv)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!(min_psnr_yuv >= 0.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_quality_floor: the floor must be >= 0 dB (+INFINITY is legal, NaN is not)");
+    e->floor_p = min_psnr_yuv;
+    return PFV_OK;
+}
+// the p-frame floor applies: it is set and there is a rung to choose
+static bool pframe_floor(const pfv_encoder *e) { return e->floor_p > 0.0 && e->hot->n_rungs > 1; }
+
 // the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
 static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
 {
@@ -611,7 +624,8 @@ static void rate_frame_written(pfv_encoder *e, bool pframe, size_t payload_bytes
     e->last_rung = s->rung;
     e->n_written++;
     e->since_iframe = pframe ? e->since_iframe + 1 : 0;
-    if (!pframe || !e->budget_p || e->pprobe_on) return;   // with the probe on the budget is the hard one: the rung was chosen before the frame was written
+    // with the probe or the p-frame floor on the budget is the hard one: the rung was chosen before the frame was written
+    if (!pframe || !e->budget_p || e->pprobe_on || pframe_floor(e)) return;
     if (payload_bytes > e->budget_p) s->rung = std::min(s->rung + 1, s->n_rungs - 1);
     else if (2 * (uint64_t)payload_bytes <= e->budget_p) s->rung = std::max(s->rung - 1, 0);
 }
@@ -698,19 +712,19 @@ static int budget_rung(const pfv_enc_session *s, const uint32_t *sizes, uint32_t
         if (sizes[r] != kEntErrOversize && sizes[r] <= budget) return r;
     return s->n_rungs - 1;
 }
-// The i-frame quality floor's rung from the probed sizes and plane sums [n_rungs][3].  Allowed: encodable and, under an i-frame budget, within
-// it.  Of the allowed rungs whose PSNR-YUV (pfv_frame_report's) reaches the floor the one with the fewest bytes; if none does, the allowed rung
+// A quality floor's rung (the i-frame's or the p-frame's, each with its own budget, 0: none) from the probed sizes and plane sums
+// [n_rungs][3].  Allowed: encodable and, under a budget, within it.  Of the allowed rungs whose PSNR-YUV (pfv_frame_report's) reaches the floor the one with the fewest bytes; if none does, the allowed rung
 // with the smallest squared error, then the fewest bytes; ties to the lower index.  No rung allowed: the coarsest, as budget_rung.
-static int floor_rung(const pfv_encoder *e, const uint32_t *sizes, const uint64_t *sse)
+static int floor_rung(const pfv_encoder *e, const uint32_t *sizes, const uint64_t *sse, uint32_t budget, double floor_db)
 {
     const pfv_enc_session *s = e->hot;
     const uint64_t samples = (uint64_t)pfv_frame_bytes(e->width, e->height);
     int meets = -1, best = -1;
     uint64_t best_sse = 0;
     for (int r = 0; r < s->n_rungs; r++) {
-        if (sizes[r] == kEntErrOversize || (e->budget_i && sizes[r] > e->budget_i)) continue;
+        if (sizes[r] == kEntErrOversize || (budget && sizes[r] > budget)) continue;
         const uint64_t total = sse[3 * r] + sse[3 * r + 1] + sse[3 * r + 2];
-        if (pfv_psnr(total, samples) >= e->floor_i && (meets < 0 || sizes[r] < sizes[meets])) meets = r;
+        if (pfv_psnr(total, samples) >= floor_db && (meets < 0 || sizes[r] < sizes[meets])) meets = r;
         if (best < 0 || total < best_sse || (total == best_sse && sizes[r] < sizes[best])) { best = r; best_sse = total; }
     }
     return meets >= 0 ? meets : best >= 0 ? best : s->n_rungs - 1;
@@ -730,7 +744,7 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
         uint64_t sse[kMaxRungs][3];
         if (!rc) rc = rd_probe_staged(s, sizes, &sse[0][0]);
         if (rc) return rc;
-        s->rung = floor_rung(e, sizes, &sse[0][0]);
+        s->rung = floor_rung(e, sizes, &sse[0][0], e->budget_i, e->floor_i);
         return PFV_OK;
     }
     if (!rc && !probed) rc = probe_staged(s, sizes);
@@ -739,11 +753,16 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
     return PFV_OK;
 }
 
-// Encoder::encode_iframe (src/enc.rs:75-123) behind pack_frame.  staged / probed: see choose_iframe_rung
-static int write_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false, const uint32_t *probed = nullptr)
+// an i-frame budget or floor applies: encode_iframe probes and chooses its rung
+static bool iframe_rung_rule(const pfv_encoder *e) { return (e->budget_i != 0 || e->floor_i > 0.0) && e->hot->n_rungs > 1; }   // one rung: nothing to choose
+
+// Encoder::encode_iframe (src/enc.rs:75-123) behind pack_frame.  staged / probed: see choose_iframe_rung; settled: the frame lies in the staging
+// and the current rung is the one to write at (pfv_encoder_encode_frame under the p-frame floor)
+static int write_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false, const uint32_t *probed = nullptr,
+                        bool settled = false)
 {
     int rc;
-    const bool budget = (e->budget_i != 0 || e->floor_i > 0.0) && e->hot->n_rungs > 1;   // one rung: nothing to choose
+    const bool budget = !settled && iframe_rung_rule(e);
     if (budget && (rc = choose_iframe_rung(e, y, u, v, staged, probed))) return rc;
     staged = staged || budget;
     if (e->device_entropy) return encode_on_device(e, false, staged);      // an i-frame replaces prev_frame entirely: clears a poisoned state
@@ -790,13 +809,14 @@ PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const 
     if (!rc) rc = rd_probe_staged(e->hot, sizes_out, sse_out);
     return rc;
 }
-// the frame up into the session's staging and sized as a p-frame at every rung (counts: [n_rungs][kPProbeStats], or nullptr)
-static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts)
+// the frame up into the session's staging and sized as a p-frame at every rung (counts: [n_rungs][kPProbeStats], or nullptr); sse
+// ([n_rungs][3], or nullptr): the rate-distortion probe in the size probe's place
+static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts, uint64_t *sse = nullptr)
 {
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
-    if (!rc) rc = pprobe_staged(e->hot, sizes, counts);
+    if (!rc) rc = sse ? prd_probe_staged(e->hot, sizes, sse, counts) : pprobe_staged(e->hot, sizes, counts);
     return rc;
 }
 // payload bytes of this frame as a p-frame against the encoder's reference at every rung; the stream, the reference and the rung stay as they are
@@ -807,6 +827,15 @@ PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uin
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr);
+}
+// ... and its squared error per plane at every rung [n_rungs][3], from the same search and transform
+PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!y || !u || !v || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_rd: null buffer");
+    if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
+    if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out);
 }
 PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
 {
@@ -825,11 +854,18 @@ PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval)
 static bool hard_pframe_budget(const pfv_encoder *e) { return e->pprobe_on && e->budget_p != 0 && e->hot->n_rungs > 1; }
 
 // Encoder::encode_pframe (src/enc.rs:125-173) behind pack_frame and the poisoned test.  staged: the frame lies in the session's staging and the
-// rung is settled (pfv_encoder_encode_frame); otherwise the hard budget, where it applies, probes the frame and chooses the rung first.
+// rung is settled (pfv_encoder_encode_frame); otherwise the p-frame floor or the hard budget, where one applies, probes the frame and chooses
+// the rung first (the floor's rule takes the budget in as a hard cap).
 static int write_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false)
 {
     int rc;
-    if (!staged && hard_pframe_budget(e)) {
+    if (!staged && pframe_floor(e)) {
+        uint32_t sizes[kMaxRungs];
+        uint64_t sse[kMaxRungs][3];
+        if ((rc = probe_pframe_planes(e, y, u, v, sizes, nullptr, &sse[0][0]))) return rc;
+        e->hot->rung = floor_rung(e, sizes, &sse[0][0], e->budget_p, e->floor_p);
+        staged = true;
+    } else if (!staged && hard_pframe_budget(e)) {
         uint32_t sizes[kMaxRungs];
         if ((rc = probe_pframe_planes(e, y, u, v, sizes, nullptr))) return rc;
         e->hot->rung = budget_rung(e->hot, sizes, e->budget_p);
@@ -867,6 +903,20 @@ static void write_dropframe(pfv_encoder *e)
     e->n_written++;
     e->since_iframe++;
 }
+// Rule 4 of pfv_encoder_encode_frame under the p-frame floor: the p-frame at rp against the i-frame at ri, each with its probed payload bytes
+// and plane sums.  A candidate meets when its PSNR-YUV reaches the P-FRAME floor; exactly one meets: that one; both: fewer bytes, ties to the
+// i-frame; neither: the smaller squared error, then fewer bytes, then the i-frame.  A candidate that is not encodable (its sums are undefined)
+// never meets and loses to one that is; neither encodable: the i-frame, as today's rule.
+static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint64_t (&psse)[3], uint32_t ibytes, const uint64_t (&isse)[3])
+{
+    if (ibytes == kEntErrOversize || pbytes == kEntErrOversize) return pbytes == kEntErrOversize;
+    const uint64_t samples = (uint64_t)pfv_frame_bytes(e->width, e->height);
+    const uint64_t pt = psse[0] + psse[1] + psse[2], it = isse[0] + isse[1] + isse[2];
+    const bool pm = pfv_psnr(pt, samples) >= e->floor_p, im = pfv_psnr(it, samples) >= e->floor_p;
+    if (pm != im) return im;
+    if (pm) return ibytes <= pbytes;
+    return it != pt ? it < pt : ibytes <= pbytes;
+}
 // The frame's type chosen by the probes; the rules, in this order, are at the declaration (include/pfv_hip_ext.h)
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out)
 {
@@ -880,11 +930,24 @@ PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uin
         rc = write_iframe(e, y, u, v);
     } else {
         uint32_t psize[kMaxRungs], isize[kMaxRungs], counts[kMaxRungs][kPProbeStats];
-        if ((rc = probe_pframe_planes(e, y, u, v, psize, &counts[0][0]))) return rc;                // 2: one upload, the p-frame sized at every rung
-        const int rp = hard_pframe_budget(e) ? budget_rung(s, psize, e->budget_p) : s->rung;
+        uint64_t psse[kMaxRungs][3], isse[kMaxRungs][3];
+        const bool rd = pframe_floor(e);
+        if ((rc = probe_pframe_planes(e, y, u, v, psize, &counts[0][0], rd ? &psse[0][0] : nullptr))) return rc;   // 2: one upload, the p-frame sized (and measured) at every rung
+        const int rp = rd ? floor_rung(e, psize, &psse[0][0], e->budget_p, e->floor_p) : hard_pframe_budget(e) ? budget_rung(s, psize, e->budget_p) : s->rung;
         if (counts[rp][kPProbeCodedAt] == 0 && counts[rp][kPProbeMovedAt] == 0) {                   // 3: nothing to code, nothing moved: a drop frame
             type = 3;
             write_dropframe(e);
+        } else if (rd) {                                                                            // 4 under the p-frame floor: the better of p at rp and i at ri
+            if ((rc = rd_probe_staged(s, isize, &isse[0][0]))) return rc;
+            const int ri = !iframe_rung_rule(e) ? s->rung : e->floor_i > 0.0 ? floor_rung(e, isize, &isse[0][0], e->budget_i, e->floor_i) : budget_rung(s, isize, e->budget_i);
+            if (rd_prefers_iframe(e, psize[rp], psse[rp], isize[ri], isse[ri])) {
+                s->rung = ri;
+                rc = write_iframe(e, y, u, v, true, nullptr, true);
+            } else {                                                                                // 5: a p-frame at rp
+                type = 2;
+                s->rung = rp;
+                rc = write_pframe(e, y, u, v, true);
+            }
         } else {
             if ((rc = probe_staged(s, isize))) return rc;                                          // 4: an i-frame that is not larger at rp
             // psize[rp] marked not encodable (0xffffffff) compares as larger than any i-frame that is encodable: the i-frame is taken

@@ -16,10 +16,12 @@ from .frame import VideoFrame
 
 class Encoder:
     def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
-                 frame_report: bool = False, qualities=None, iframe_budget: int = 0, iframe_quality_floor: float = 0.0):
+                 frame_report: bool = False, qualities=None, iframe_budget: int = 0, iframe_quality_floor: float = 0.0,
+                 pframe_quality_floor: float = 0.0):
         """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
         quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame.  ``iframe_budget``: see
-        ``set_iframe_budget``; ``iframe_quality_floor``: see ``set_iframe_quality_floor``"""
+        ``set_iframe_budget``; ``iframe_quality_floor``: see ``set_iframe_quality_floor``; ``pframe_quality_floor``: see
+        ``set_pframe_quality_floor``"""
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
         h = ctypes.c_void_p()
@@ -40,6 +42,8 @@ class Encoder:
             ctx.check(ctx._lib.pfv_encoder_set_iframe_budget(h, int(iframe_budget)))
         if iframe_quality_floor:
             ctx.check(ctx._lib.pfv_encoder_set_iframe_quality_floor(h, float(iframe_quality_floor)))
+        if pframe_quality_floor:
+            ctx.check(ctx._lib.pfv_encoder_set_pframe_quality_floor(h, float(pframe_quality_floor)))
         self.finished = False
         ctx._sessions.add(self)
         self._flush()                                               # header (src/enc.rs:70)
@@ -133,6 +137,23 @@ class Encoder:
         self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
                                                               ptr(frame.plane_v.pixels), ptr(sizes)))
         return sizes
+
+    def probe_pframe_rd(self, frame: VideoFrame):
+        """(sizes uint32 [n_rungs], sse uint64 [n_rungs, 3]) of `frame` as a p-frame against the encoder's reference at every rung: payload
+        bytes as probe_pframe and the squared error per plane a frame report would show at that rung; the stream, the reference and the rung
+        stay as they are.  PfvError(PFV_ERR_STATE) when poisoned or finished"""
+        import numpy as np
+        sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe_rd(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
+                                                                 ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse)))
+        return sizes, sse
+
+    def set_pframe_quality_floor(self, min_psnr_yuv: float = 0.0):
+        """PSNR-YUV floor in dB per p-frame (0: off; inf: the best-looking rung that fits): encode_pframe probes size and squared error at
+        every rung and takes, of the rungs within the set_rate budget (a hard cap here) that reach the floor, the one with the fewest bytes
+        -- if none does, the one with the smallest error; encode_frame then weighs that p-frame against the i-frame by the same measure
+        (pfv_encoder_set_pframe_quality_floor)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_pframe_quality_floor(self.handle, float(min_psnr_yuv)))
 
     def set_pframe_probe(self, on: bool = True):
         """on, with a set_rate budget and more than one rung: encode_pframe probes the frame and encodes it at the finest rung whose payload

@@ -121,6 +121,23 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
                                                               ctypes.c_void_p(stats_dev or 0)))
 
+    # p-frame rate-distortion probe ---------------------------------------
+    def probe_pframe_rd(self, frames):
+        """(sizes uint32 [n_streams, n_rungs], sse uint64 [n_streams, n_rungs, 3]) of every stream's frame as a p-frame against the current
+        prev_frame at every rung, from one search and one transform (pfv_enc_probe_pframe_rd): payload bytes as probe_pframe, squared error
+        per plane (Y, U, V) against the reconstruction that rung would leave in prev_frame.  Leaves prev_frame and the rung alone."""
+        f = self._frames(frames)
+        sizes = np.zeros((self.n_streams, self.n_rungs), dtype=np.uint32)
+        sse = np.zeros((self.n_streams, self.n_rungs, 3), dtype=np.uint64)
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_rd(self.handle, ptr(f), ptr(sizes), ptr(sse)))
+        return sizes, sse
+
+    def probe_pframe_rd_dev(self, frames_dev: int, sizes_dev: int, sse_dev: int, stats_dev: int = 0):
+        """asynchronous on the context's stream; sizes_dev uint32 [n_streams][n_rungs], sse_dev uint64 [n_streams][n_rungs][3], stats_dev
+        uint32 [n_streams][n_rungs][20] or 0.  Honours the window and the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_rd_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
+                                                                 ctypes.c_void_p(sse_dev), ctypes.c_void_p(stats_dev or 0)))
+
     # host-buffer forms ------------------------------------------------
     def _frames(self, frames) -> np.ndarray:
         f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)

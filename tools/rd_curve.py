@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -31,6 +31,13 @@ and probed against reported squared error per rung -- and then its timing at 96 
 A = the probe's two launches (k_probe_iframe_rd + k_probe_rd_sizes); B = the way to the same numbers without it, per rung
 pfv_enc_session_set_rung + pfv_enc_iframe_dev + the entropy stage to the size + pfv_enc_distortion_dev; C = pfv_enc_probe_iframe_dev alone
 (what the distortion half adds is A - C).  The answers are compared rung by rung over all streams.
+
+--probe-p-rd: the p-frame rate-distortion probe (pfv_encoder_probe_pframe_rd) on the clip's second frame behind its first -- probed against
+written payload bytes and reported squared error per rung -- and then its timing at 96 x 1080p by --probe-p's method: A = the probe's two
+launches (k_probe_pframe_rd + k_pprobe_rd_sizes); B = per rung pfv_enc_session_set_rung + pfv_enc_pframe_dev + pfv_enc_pack_pframe_dev to the
+size + pfv_enc_distortion_dev, the i-frame that restores prev_frame enqueued outside the rung's event pair; C = pfv_enc_probe_pframe_dev alone.
+Sizes and plane sums against the trial encodes at every rung of all streams; then the host clock around pfv_encoder: encode_pframe and
+encode_frame with the p-frame quality floor off / on.
 """
 import argparse
 import ctypes
@@ -445,6 +452,141 @@ def pprobe_sizes_line(pkg, ctx, w, h, kind, ladder):
     return {"ladder": ladder, "width": w, "height": h, "kind": kind, "probed_bytes": probed, "written_bytes": written, "equal": probed == written}
 
 
+def pprobe_rd_line(pkg, ctx, w, h, kind, ladder):
+    """probed against written payload bytes and reported squared error of the clip's second frame as a p-frame behind its first at every rung"""
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    f0, f1 = (pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in (0, 1))
+    enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, frame_report=True, qualities=ladder)
+    probed, probed_sse, written, reported, psnr = None, None, [], [], []
+    for r in range(len(ladder)):
+        enc.set_rung(len(ladder) // 2)
+        enc.encode_iframe(f0)
+        sizes, sse = enc.probe_pframe_rd(f1)
+        probed, probed_sse = [int(v) for v in sizes], [[int(v) for v in row] for row in sse]
+        enc.set_rung(r)
+        enc.encode_pframe(f1)
+        rep = enc.last_report
+        written.append(rep.packet_bytes - 5)
+        reported.append([int(v) for v in rep.sse])
+        psnr.append(rep.psnr_yuv)
+    enc.close()
+    return {"ladder": ladder, "width": w, "height": h, "kind": kind, "probed_bytes": probed, "written_bytes": written, "probed_sse": probed_sse,
+            "reported_sse": reported, "psnr_yuv": psnr, "equal": probed == written and probed_sse == reported}
+
+
+def time_probe_p_rd(pkg, ctx, n_streams, ladder, w=1920, h=1080, warmup=3, samples=20, rounds=3):
+    lib = ctx._lib
+    fb, tb, R = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h)), len(ladder)
+    mid = R // 2
+    f0, f1 = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    sizes, sse, sse_b = ctx.alloc(n_streams * R * 4), ctx.alloc(n_streams * R * 24), ctx.alloc(n_streams * 24)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    probe = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full.enable_entropy()
+    upto.enable_entropy(payload_cap=24)            # the stage "up to the size", as time_probe_p
+    probe.set_rung(mid)
+    probe.encode_iframe_dev(f0, coef)              # the state every measurement starts from: frame 0 as an i-frame at the middle rung
+    ev = [(ctx.event(), ctx.event()) for _ in range(R)]
+
+    def elapsed(pair):
+        ms = ctypes.c_float()
+        ctx.check(lib.pfv_event_elapsed_ms(pair[0], pair[1], ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sample(fn):
+        ctx.record(ev[0][0])
+        fn()
+        ctx.record(ev[0][1])
+        return elapsed(ev[0])
+
+    def sample_trials():
+        for r in range(R):
+            upto.set_rung(mid)
+            upto.encode_iframe_dev(f0, coef)       # outside the pair: prev_frame back to the state the probe sees
+            ctx.record(ev[r][0])
+            upto.set_rung(r)
+            upto.encode_pframe_dev(f1, mv, has, coef)
+            upto.pack_pframe_dev(mv, has, coef)
+            upto.distortion_dev(f1, sse_b)
+            ctx.record(ev[r][1])
+        return sum(elapsed(p) for p in ev)
+
+    def median_ms(fn):
+        got = [fn() for _ in range(warmup + samples)]
+        return statistics.median(got[warmup:])
+    res = {"rd_probe": [], "trials": [], "size_probe": []}
+    for _ in range(rounds):
+        res["rd_probe"].append(median_ms(lambda: sample(lambda: probe.probe_pframe_rd_dev(f1, sizes, sse))))
+        res["trials"].append(median_ms(sample_trials))
+        res["size_probe"].append(median_ms(lambda: sample(lambda: probe.probe_pframe_dev(f1, sizes))))
+    # the answers: the probe's against the trial encodes' (rung by rung, all streams)
+    probe.probe_pframe_rd_dev(f1, sizes, sse)
+    got, got_sse = np.zeros((n_streams, R), np.uint32), np.zeros((n_streams, R, 3), np.uint64)
+    ctx.download(got, sizes)
+    ctx.download(got_sse, sse)
+    same_sizes, same_sse = [], []
+    one = np.zeros((n_streams, 3), np.uint64)
+    for r in range(R):
+        full.set_rung(mid)
+        full.encode_iframe_dev(f0, coef)
+        full.set_rung(r)
+        full.encode_pframe_dev(f1, mv, has, coef)
+        full.pack_pframe_dev(mv, has, coef)
+        full.distortion_dev(f1, sse_b)
+        same_sizes.append(bool(np.array_equal(full.payload_sizes(), got[:, r])))
+        ctx.download(one, sse_b)
+        same_sse.append(bool(np.array_equal(one, got_sse[:, r])))
+    for a, b in ev:
+        ctx.event_destroy(a); ctx.event_destroy(b)
+    for s_ in (probe, full, upto):
+        s_.close()
+    for p in (f0, f1, coef, mv, has, sizes, sse, sse_b):
+        ctx.free(p)
+    a, b, c = (statistics.median(res[k]) for k in ("rd_probe", "trials", "size_probe"))
+    spread = {k: max(v) - min(v) for k, v in res.items()}
+    samples_n = n_streams * fb
+    return {"shape": f"{n_streams} x {w}x{h}", "ladder": ladder, "samples_per_round": samples, "rounds": rounds,
+            "A_rd_probe_ms": a, "B_trials_ms": b, "C_size_probe_ms": c, "spread_ms": spread, "A_over_B": a / b if b else None,
+            "A_below_B_by_more_than_Bs_spread": bool(a < b - spread["trials"]), "distortion_half_ms": a - c,
+            "distortion_half_ms_per_rung": (a - c) / R, "rounds_ms": res,
+            "sizes_equal_per_rung": same_sizes, "sse_equal_per_rung": same_sse, "bytes_stream0": [int(v) for v in got[0]],
+            "psnr_yuv_all_streams": [pkg.psnr(int(got_sse[:, r].sum()), samples_n) for r in range(R)]}
+
+
+def time_pframe_floor_modes(pkg, ctx, ladder, w=1920, h=1080, n=14, rounds=3):
+    """host milliseconds per frame of one pfv_encoder behind an i-frame: encode_pframe and encode_frame, p-frame quality floor off / on (a
+    floor the middle rung of frame 1 meets)"""
+    st = pkg.SyntheticStream(w, h)
+    frs = [pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in range(n)]
+    per = {"pframe": [], "pframe_floor": [], "encode_frame": [], "encode_frame_floor": []}
+    seen = {k: set() for k in per}
+    for _ in range(rounds):
+        for mode in per:
+            enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, qualities=ladder)
+            enc.set_rung(len(ladder) // 2)
+            enc.encode_iframe(frs[0])
+            if mode.endswith("_floor"):
+                sse = enc.probe_pframe_rd(frs[1])[1]
+                enc.set_pframe_quality_floor(pkg.psnr(int(sse[len(ladder) // 2].sum()), int(ctx._lib.pfv_frame_bytes(w, h))))
+            secs = []
+            for fr in frs[1:]:
+                t0 = time.perf_counter()
+                kind = enc.encode_frame(fr) if mode.startswith("encode_frame") else (enc.encode_pframe(fr), 2)[1]
+                secs.append(time.perf_counter() - t0)
+                seen[mode].add((kind, enc.rung))
+            enc.close()
+            per[mode].append(statistics.median(secs[1:]) * 1e3)
+    out = {"shape": f"1 x {w}x{h}", "ladder": ladder, "rounds_ms": per, "types_and_rungs_seen": {k: sorted(v) for k, v in seen.items()}}
+    for k, v in per.items():
+        out[k + "_ms"] = statistics.median(v)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("width", type=int)
@@ -457,6 +599,7 @@ def main():
     ap.add_argument("--probe", action="store_true")
     ap.add_argument("--probe-p", action="store_true")
     ap.add_argument("--probe-rd", action="store_true")
+    ap.add_argument("--probe-p-rd", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -490,6 +633,14 @@ def main():
                 return
             for lad in ([0, 2, 5, 7, 10], list(range(11))):
                 print(json.dumps({"probe_rd_timing": time_probe_rd(pkg, ctx, 96, lad)}), flush=True)
+        if a.probe_p_rd:
+            ladder = [int(x) for x in a.qualities.split(",") if x != ""]
+            print(json.dumps({"pprobe_rd": pprobe_rd_line(pkg, ctx, a.width, a.height, a.kind, ladder)}), flush=True)
+            if os.environ.get("PFV_HIP_LIB"):          # another build of the C ABI (the CPU emulator): nothing to time
+                return
+            for lad in ([0, 2, 5, 7, 10], list(range(11))):
+                print(json.dumps({"pprobe_rd_timing": time_probe_p_rd(pkg, ctx, 96, lad)}), flush=True)
+            print(json.dumps({"pprobe_rd_encoder_latency": time_pframe_floor_modes(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
 
 
 if __name__ == "__main__":
