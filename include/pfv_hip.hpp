@@ -11,6 +11,7 @@
 // Header-only; link against libpfv_hip.so.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <istream>
@@ -99,6 +100,24 @@ struct FrameReport {
     double psnr_yuv = 0;
 };
 
+// structural similarity (pfv_hip_ext.h, "structural similarity on the device"): the mean of `windows` window values summed in 2^-24 fixed
+// point; NaN for windows == 0
+inline double ssim(int64_t q24_sum, uint64_t windows) { return pfv_ssim(q24_sum, windows); }
+// SSIM windows per plane (Y, U, V) of a width x height frame
+inline std::array<uint32_t, 3> ssim_windows(size_t width, size_t height)
+{
+    std::array<uint32_t, 3> out{};
+    if (pfv_ssim_windows((int)width, (int)height, out.data()) != PFV_OK) throw Error(PFV_ERR_BAD_ARG, "ssim_windows: width/height must be positive, even and fit u16");
+    return out;
+}
+// the structural similarity between the frame one Encoder::encode_* call was given and its reconstruction (pfv_frame_ssim)
+struct FrameSsim {
+    int64_t q24[3] = {0, 0, 0};      // Y, U, V; zeros for a drop frame
+    uint32_t windows[3] = {0, 0, 0};
+    double ssim[3] = {0, 0, 0};      // per plane
+    double ssim_all = 0;             // over all windows of the frame
+};
+
 // src/enc.rs:12-188
 class Encoder {
   public:
@@ -154,6 +173,8 @@ class Encoder {
     void set_device_entropy(bool on) { ctx_.check(pfv_encoder_set_device_entropy(h_, on ? 1 : 0)); }
     // on: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
     void set_frame_report(bool on) { ctx_.check(pfv_encoder_set_frame_report(h_, on ? 1 : 0)); }
+    // on: every encode_* call also measures the structural similarity of the same pair of frames (last_ssim); a switch of its own; same bytes
+    void set_frame_ssim(bool on) { ctx_.check(pfv_encoder_set_frame_ssim(h_, on ? 1 : 0)); }
     // quality ladder: the rung of the frames that follow / of the last frame written (before the first frame: the current rung)
     void set_rung(int rung) { ctx_.check(pfv_encoder_set_rung(h_, rung)); }
     int rung() const { return pfv_encoder_rung(h_); }
@@ -226,6 +247,16 @@ class Encoder {
         out.packet_bytes = r.packet_bytes;
         for (int i = 0; i < 3; i++) { out.sse[i] = r.sse[i]; out.psnr[i] = r.psnr[i]; }
         out.psnr_yuv = r.psnr_yuv;
+        return out;
+    }
+    // of the last encode_* call; Error(PFV_ERR_STATE) when set_frame_ssim is off, nothing has been encoded yet or that call failed
+    FrameSsim last_ssim() const
+    {
+        pfv_frame_ssim r;
+        ctx_.check(pfv_encoder_frame_ssim(h_, &r));
+        FrameSsim out;
+        for (int i = 0; i < 3; i++) { out.q24[i] = r.q24[i]; out.windows[i] = r.windows[i]; out.ssim[i] = r.ssim[i]; }
+        out.ssim_all = r.ssim_all;
         return out;
     }
 

@@ -308,6 +308,54 @@ PFV_API int pfv_encoder_set_frame_report(pfv_encoder *e, int on);               
 /* of the last encode_* call; PFV_ERR_STATE when reports are off, no frame has been encoded, or that call failed */
 PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out);
 
+/* ------------------------------------------------------------------ structural similarity on the device  [B]
+ * Squared error rates the blocking of a coarse rung far too kindly; this is the structural similarity index (SSIM) in the integer form the
+ * common video tools use -- 8 x 8 windows at stride 4, so windows straddle the edges of the 8 x 8 transform blocks -- measured where the
+ * frames lie.  Operands, layouts, strides and the scratch rule are those of pfv_frames_sse_dev.  Per plane (w x h, 8-bit), on its own:
+ *   blocks    bw = w >> 2, bh = h >> 2 blocks of 4 x 4 pixels; pixels beyond 4 bw or 4 bh belong to no block, padding never counts.
+ *             Per block, in integers: s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum ab.
+ *   windows   one per (bx, by) with bx + 1 < bw and by + 1 < bh: the sums of blocks (bx, by), (bx + 1, by), (bx, by + 1), (bx + 1, by + 1) added
+ *             together (64 pixels); max(0, bw - 1) * max(0, bh - 1) per plane (pfv_ssim_windows).
+ *   value     c1 = 416, c2 = 235963 ((0.01 * 255)^2 * 64 and (0.03 * 255)^2 * 64 * 63, rounded);
+ *                 vars = 64 ss - s1^2 - s2^2       covar = 64 s12 - s1 s2
+ *                 n1 = 2 s1 s2 + c1   n2 = 2 covar + c2   d1 = s1^2 + s2^2 + c1   d2 = vars + c2      (exact in int32, all below 2^30)
+ *                 ssim = (f32(n1) * f32(n2)) / (f32(d1) * f32(d2))      IEEE single precision, a true division; in [-1, 1]
+ *                 q = rint(ssim * 2^24) as int32, round to nearest even
+ *   ssim_q24_dev     int64_t[n_streams][3] (Y, U, V): the sum of q over the plane's windows
+ *   mb_ssim_q24_dev  int32_t[n_streams][pfv_total_blocks], the index space of mv / has_coef: the sum of q over the windows whose top-left
+ *                    pixel lies in the macroblock (at most 16, so |entry| <= 2^28; 0 without windows), or NULL: the map then goes to scratch
+ *                    of the context / session under the rule of pfv_frames_sse_dev (PFV_ERR_STATE when that needs an allocation inside a
+ *                    graph recording).
+ * Every entry of both outputs is written by every call; nothing is accumulated or cleared, and there are no atomics: integer sums do not
+ * depend on launch shape or arrival order, so two calls on the same input, and any graph replay, are bit-identical.  Two launches, k_ssim_mb +
+ * k_ssim_sum (csrc/pfv_ssim_kernels.hip).  Measured on one MI355X, 96 x 1080p, packed against padded: see profiles/quality_ssim.md. */
+PFV_API int pfv_frames_ssim_dev(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *a_dev, int a_layout, size_t a_stride,
+                                const uint8_t *b_dev, int b_layout, size_t b_stride, int64_t *ssim_q24_dev, int32_t *mb_ssim_q24_dev);
+/* host buffers, both PACKED; mb_out may be NULL; synchronises */
+PFV_API int pfv_frames_ssim(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *a, const uint8_t *b, int64_t *ssim_q24_out,
+                            int32_t *mb_out);
+/* windows per plane (Y, U, V) of a width x height frame; PFV_ERR_BAD_ARG for dimensions a frame cannot have */
+PFV_API int pfv_ssim_windows(int width, int height, uint32_t out[3]);
+/* q24_sum / (2^24 * windows) in double: the mean SSIM of the windows; NaN when windows == 0 */
+PFV_API double pfv_ssim(int64_t q24_sum, uint64_t windows);
+/* the sessions' own comparisons: operands, window, frame / output stride and slot semantics of pfv_enc_distortion_dev /
+ * pfv_dec_distortion_dev; entries of slots outside the window are left alone */
+PFV_API int pfv_enc_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, int64_t *ssim_q24_dev, int32_t *mb_dev);
+PFV_API int pfv_dec_ssim_dev(pfv_dec_session *s, const uint8_t *frames_dev, int64_t *ssim_q24_dev, int32_t *mb_dev);
+/* pfv_encoder: the SSIM between the frame the last encode_* call was given and its reconstruction.  A switch of its own, independent of the
+ * frame reports: with it on, one more pair of small launches follows the encode kernel and 24 bytes come back with the payload size (or with
+ * the host path's downloads); the stream bytes are the same.  pfv_gop_encoder and pfv_batch_encoder have none, for the reason given for
+ * the reports. */
+typedef struct pfv_frame_ssim {
+    int64_t  q24[3];      /* Y,U,V; zeros for a drop frame */
+    uint32_t windows[3];
+    double   ssim[3];     /* pfv_ssim per plane; 1 for a drop frame */
+    double   ssim_all;    /* pfv_ssim(sum of q24, sum of windows); 1 for a drop frame */
+} pfv_frame_ssim;
+PFV_API int pfv_encoder_set_frame_ssim(pfv_encoder *e, int on);                 /* default 0 */
+/* of the last encode_* call; PFV_ERR_STATE when the switch is off, no frame has been encoded, or that call failed */
+PFV_API int pfv_encoder_frame_ssim(pfv_encoder *e, pfv_frame_ssim *out);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

@@ -157,6 +157,14 @@ SIGNATURES = [
     ("pfv_dec_distortion_dev", c_int, [_P, _P, _P, _P]),
     ("pfv_encoder_set_frame_report", c_int, [_P, c_int]),
     ("pfv_encoder_frame_report", c_int, [_P, _P]),
+    ("pfv_frames_ssim_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, _P, c_int, c_size_t, _P, _P]),
+    ("pfv_frames_ssim", c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    ("pfv_ssim_windows", c_int, [c_int, c_int, _P]),
+    ("pfv_ssim", ctypes.c_double, [ctypes.c_int64, ctypes.c_uint64]),
+    ("pfv_enc_ssim_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_dec_ssim_dev", c_int, [_P, _P, _P, _P]),
+    ("pfv_encoder_set_frame_ssim", c_int, [_P, c_int]),
+    ("pfv_encoder_frame_ssim", c_int, [_P, _P]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

@@ -1,13 +1,14 @@
 // pfv_context.hip -- context: pfv_ctx, options, timing events, HIP graphs (pfv_ctx_*, pfv_event_*, pfv_graph_*).
 // Part of the one translation unit of the C ABI: included by pfv_capi.hip, in this order, never compiled on its own.
 // ------------------------------------------------------------------ context
+constexpr int kCtxScratch = 9;   // slots 0..5, 7: plane operators and host-pointer forms; 6: pfv_quality.hip's map; 8: pfv_ssim.hip's map
 struct pfv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
     // grow-only device scratch for the host-pointer entry points
-    void *scratch[8] = {};
-    size_t scratch_cap[8] = {};
+    void *scratch[kCtxScratch] = {};
+    size_t scratch_cap[kCtxScratch] = {};
     QTab *qtab_dev = nullptr;    // 4 slots
     QTab *qtab_host = nullptr;   // pinned mirror
     int *flag_dev = nullptr;
@@ -191,7 +192,7 @@ PFV_API void pfv_ctx_destroy(pfv_ctx *ctx)
         auto &v = ctx->owner->children;
         v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
     }
-    for (int i = 0; i < 8; i++)
+    for (int i = 0; i < kCtxScratch; i++)
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->qtab_dev) (void)hipFree(ctx->qtab_dev);
     if (ctx->qtab_host) (void)hipHostFree(ctx->qtab_host);

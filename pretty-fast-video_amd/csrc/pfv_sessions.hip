@@ -105,6 +105,10 @@ struct pfv_enc_session {
     uint32_t *q_map = nullptr;
     uint64_t *q_sse = nullptr;
     uint64_t *report_host = nullptr;         // pfv_encoder's frame reports are on: [n_streams][3], page-locked, owned by the encoder
+    // structural similarity (pfv_ssim.hip): the same three for the SSIM sums
+    int32_t *ssim_map = nullptr;
+    int64_t *ssim_sums = nullptr;
+    int64_t *ssim_host = nullptr;            // pfv_encoder's frame SSIM is on: [n_streams][3], page-locked, owned by the encoder
     // i-frame size probe (pfv_probe.hip): the kernels' accumulator [n_streams][n_rungs][kProbeAcc], zero between calls; sizes of the host-buffer form
     uint32_t *probe_acc = nullptr;
     uint32_t *probe_sizes = nullptr;
@@ -158,8 +162,10 @@ struct pfv_dec_session {
     int16_t *st_val = nullptr;
     size_t st_sparse_cap = 0;
     uint32_t *q_map = nullptr;               // distortion (pfv_quality.hip): the macroblock map when the caller passes none
+    int32_t *ssim_map = nullptr;             // structural similarity (pfv_ssim.hip): the same
 };
 static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
+static int enc_ssim_enqueue(pfv_enc_session *s);     // pfv_ssim.hip
 
 extern "C" {
 
@@ -238,7 +244,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -359,6 +365,7 @@ static int enc_iframe_host(pfv_enc_session *s, const uint8_t *frames, int16_t *c
                                     hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_iframe_dev(s, s->st_frames, s->st_coef))) return rc;
     if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
+    if (s->ssim_host && (rc = enc_ssim_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
@@ -384,6 +391,7 @@ static int enc_pframe_host(pfv_enc_session *s, const uint8_t *frames, int8_t *mv
                                     hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pfv_enc_pframe_dev(s, s->st_frames, s->st_mv, s->st_has, s->st_coef))) return rc;
     if (s->report_host && (rc = enc_report_enqueue(s))) return rc;
+    if (s->ssim_host && (rc = enc_ssim_enqueue(s))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(coef_out, s->st_coef, n * 512, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(mv_out, s->st_mv, n * 2, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(has_coef_out, s->st_has, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -686,7 +694,7 @@ PFV_API void pfv_dec_session_destroy(pfv_dec_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map};
+    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map, s->ssim_map};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;

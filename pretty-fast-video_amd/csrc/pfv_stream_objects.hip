@@ -75,6 +75,11 @@ struct pfv_encoder {
     int report_state = 0;                  // 0: no encode_* call yet, 1: `report` describes the last one, -1: the last one failed
     pfv_frame_report report{};
     PinnedBuf<uint64_t> sums;              // [3]
+    // frame SSIM (pfv_encoder_set_frame_ssim): a switch of its own, the same life cycle
+    bool ssim_on = false;
+    int ssim_state = 0;                    // as report_state
+    pfv_frame_ssim ssim{};
+    PinnedBuf<int64_t> ssim_sums;          // [3]
     // quality ladder (pfv_encoder_create_ladder): the current rung is the session's; rate control (pfv_encoder_set_rate)
     int last_rung = -1;                    // rung of the last frame written (-1: none yet)
     uint32_t budget_p = 0;                 // p-frame payload bytes; 0: off
@@ -580,8 +585,10 @@ PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr
 static bool pframe_floor(const pfv_encoder *e) { return e->floor_p > 0.0 && e->hot->n_rungs > 1; }
 
 // the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
+static void fill_ssim(pfv_encoder *e, int type);
 static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
 {
+    fill_ssim(e, type);
     if (!e->report_on) return;
     pfv_frame_report &r = e->report;
     const uint64_t ny = (uint64_t)e->width * (uint64_t)e->height, nc = (uint64_t)(e->width / 2) * (uint64_t)(e->height / 2);
@@ -593,6 +600,24 @@ static void fill_report(pfv_encoder *e, int type, size_t packet_bytes)
     }
     r.psnr_yuv = pfv_psnr(r.sse[0] + r.sse[1] + r.sse[2], ny + 2 * nc);
     e->report_state = 1;
+}
+
+// the frame SSIM of the same call (type 3: a drop frame, nothing measured: zeros, and the value of identical frames)
+static void fill_ssim(pfv_encoder *e, int type)
+{
+    if (!e->ssim_on) return;
+    pfv_frame_ssim &r = e->ssim;
+    (void)pfv_ssim_windows(e->width, e->height, r.windows);
+    int64_t all = 0;
+    uint64_t n_all = 0;
+    for (int i = 0; i < 3; i++) {
+        r.q24[i] = type == 3 ? 0 : e->ssim_sums.data()[i];
+        r.ssim[i] = type == 3 ? 1.0 : pfv_ssim(r.q24[i], r.windows[i]);
+        all += r.q24[i];
+        n_all += r.windows[i];
+    }
+    r.ssim_all = type == 3 ? 1.0 : pfv_ssim(all, n_all);
+    e->ssim_state = 1;
 }
 
 static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
@@ -661,6 +686,7 @@ static int encode_on_device(pfv_encoder *e, bool pframe, bool staged = false)
     // from here on prev_frame has moved to this frame: a failure leaves the encoder's reference ahead of the stream
     e->poisoned = true;
     if (e->report_on && (rc = enc_report_enqueue(s))) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // arrives with the payload size
+    if (e->ssim_on && (rc = enc_ssim_enqueue(s))) { (void)hipStreamSynchronize(ctx->stream); return rc; }       // and so do these
     rc = pframe ? pfv_enc_pack_pframe_dev(s, s->st_mv, s->st_has, s->st_coef) : pfv_enc_pack_iframe_dev(s, s->st_coef);
     uint32_t nbytes = 0;
     if (!rc) rc = pfv_enc_payload_sizes(s, &nbytes);
@@ -702,6 +728,28 @@ PFV_API int pfv_encoder_frame_report(pfv_encoder *e, pfv_frame_report *out)
     if (e->report_state == 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_report: no frame has been encoded yet");
     if (e->report_state < 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_report: the last encode call failed");
     *out = e->report;
+    return PFV_OK;
+}
+
+// Frame SSIM: with it on, every encode_* call also measures the structural similarity between the frame it was given and the reconstruction
+// it leaves in prev_frame (k_ssim_mb + k_ssim_sum behind the encode kernel); the stream bytes do not change.
+PFV_API int pfv_encoder_set_frame_ssim(pfv_encoder *e, int on)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (on && !e->ssim_sums.resize(3)) return fail(e->ctx, PFV_ERR_NOMEM, "pinned staging for the frame SSIM");
+    int rc = enc_ssim_enable(e->hot, on ? e->ssim_sums.data() : nullptr);
+    if (rc) return rc;
+    if (!on || !e->ssim_on) e->ssim_state = 0;
+    e->ssim_on = on != 0;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_frame_ssim(pfv_encoder *e, pfv_frame_ssim *out)
+{
+    if (!e || !out) return fail(e ? e->ctx : nullptr, PFV_ERR_BAD_ARG, "pfv_encoder_frame_ssim: bad argument");
+    if (!e->ssim_on) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_ssim: frame SSIM is off (pfv_encoder_set_frame_ssim)");
+    if (e->ssim_state == 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_ssim: no frame has been encoded yet");
+    if (e->ssim_state < 0) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_frame_ssim: the last encode call failed");
+    *out = e->ssim;
     return PFV_OK;
 }
 
@@ -783,6 +831,7 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    if (e->ssim_on) e->ssim_state = -1;
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     return write_iframe(e, y, u, v);
@@ -889,6 +938,7 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    if (e->ssim_on) e->ssim_state = -1;
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     // a previous frame failed after the encoder's reference had advanced but before its packet was written: a p-frame
@@ -922,6 +972,7 @@ PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uin
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
+    if (e->ssim_on) e->ssim_state = -1;
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     pfv_enc_session *s = e->hot;
@@ -968,6 +1019,7 @@ PFV_API int pfv_encoder_encode_dropframe(pfv_encoder *e)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;
+    if (e->ssim_on) e->ssim_state = -1;
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:176)");
     write_dropframe(e);
     return PFV_OK;

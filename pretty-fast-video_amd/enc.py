@@ -17,7 +17,7 @@ from .frame import VideoFrame
 class Encoder:
     def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
                  frame_report: bool = False, qualities=None, iframe_budget: int = 0, iframe_quality_floor: float = 0.0,
-                 pframe_quality_floor: float = 0.0):
+                 pframe_quality_floor: float = 0.0, frame_ssim: bool = False):
         """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
         quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame.  ``iframe_budget``: see
         ``set_iframe_budget``; ``iframe_quality_floor``: see ``set_iframe_quality_floor``; ``pframe_quality_floor``: see
@@ -38,6 +38,9 @@ class Encoder:
         # frame_report: every encode_* call also measures its frame against the reconstruction it leaves behind (last_report); same bytes
         if frame_report:
             ctx.check(ctx._lib.pfv_encoder_set_frame_report(h, 1))
+        # frame_ssim: a switch of its own -- the structural similarity of the same pair of frames (last_ssim); same bytes
+        if frame_ssim:
+            ctx.check(ctx._lib.pfv_encoder_set_frame_ssim(h, 1))
         if iframe_budget:
             ctx.check(ctx._lib.pfv_encoder_set_iframe_budget(h, int(iframe_budget)))
         if iframe_quality_floor:
@@ -181,6 +184,15 @@ class Encoder:
         r = FrameReportStruct()
         self.ctx.check(self.ctx._lib.pfv_encoder_frame_report(self.handle, ctypes.byref(r)))
         return FrameReport(int(r.type), int(r.packet_bytes), tuple(int(v) for v in r.sse), tuple(float(v) for v in r.psnr), float(r.psnr_yuv))
+
+    @property
+    def last_ssim(self):
+        """FrameSsim of the last encode_* call (pfv_encoder_frame_ssim); PfvError(PFV_ERR_STATE) when frame_ssim is off, nothing has been
+        encoded yet or that call failed"""
+        from .quality import FrameSsim, FrameSsimStruct
+        r = FrameSsimStruct()
+        self.ctx.check(self.ctx._lib.pfv_encoder_frame_ssim(self.handle, ctypes.byref(r)))
+        return FrameSsim(tuple(int(v) for v in r.q24), tuple(int(v) for v in r.windows), tuple(float(v) for v in r.ssim), float(r.ssim_all))
 
     def finish(self):
         assert not self.finished                                    # src/enc.rs:183

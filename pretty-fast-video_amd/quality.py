@@ -1,6 +1,7 @@
 """Distortion measured on the device (include/pfv_hip_ext.h, "distortion on the device"): squared error per plane and per
-macroblock between frames, PSNR, and the frame report of :class:`Encoder`.  The sums come from the k_sse_* kernels
-(csrc/pfv_quality_kernels.hip); this module only marshals.
+macroblock between frames, PSNR, and the frame report of :class:`Encoder`; and structural similarity ("structural similarity on the
+device"): the SSIM sums per plane and per macroblock in 2^-24 fixed point, the mean from them, and the frame SSIM of :class:`Encoder`.
+The sums come from the k_sse_* and k_ssim_* kernels (csrc/pfv_quality_kernels.hip, csrc/pfv_ssim_kernels.hip); this module only marshals.
 """
 from __future__ import annotations
 
@@ -32,6 +33,48 @@ def frames_sse(ctx: Context, width: int, height: int, a, b, mb_map: bool = False
     return (sse, mb) if mb_map else sse
 
 
+def ssim(q24_sum: int, windows: int) -> float:
+    """q24_sum / (2^24 windows) in double: the mean SSIM of the windows; nan for windows == 0 (pfv_ssim)"""
+    return float(_lib.load().pfv_ssim(int(q24_sum), int(windows)))
+
+
+def ssim_windows(width: int, height: int) -> tuple:
+    """SSIM windows per plane (Y, U, V) of a width x height frame (pfv_ssim_windows)"""
+    out = (ctypes.c_uint32 * 3)()
+    rc = _lib.load().pfv_ssim_windows(int(width), int(height), out)
+    if rc != _lib.PFV_OK:
+        raise _lib.PfvError(rc, "pfv_ssim_windows: width/height must be positive, even and fit u16")
+    return tuple(int(v) for v in out)
+
+
+def frames_ssim(ctx: Context, width: int, height: int, a, b, mb_map: bool = False):
+    """SSIM sums between packed Y|U|V frames `a` and `b` (uint8, n frames each): int64 [n, 3] per plane in 2^-24 fixed point (divide with
+    :func:`ssim` by :func:`ssim_windows`), and with mb_map the per-macroblock map int32 [n, total_blocks] as well (pfv_frames_ssim)"""
+    fb = int(ctx._lib.pfv_frame_bytes(int(width), int(height)))
+    fa = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    fb_ = fa if b is a else np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+    assert fb > 0 and fa.size == fb_.size and fa.size % fb == 0 and fa.size
+    n = fa.size // fb
+    sums = np.zeros((n, 3), dtype=np.int64)
+    mb = np.zeros((n, int(ctx._lib.pfv_total_blocks(int(width), int(height)))), dtype=np.int32) if mb_map else None
+    ctx.check(ctx._lib.pfv_frames_ssim(ctx.handle, int(width), int(height), n, ptr(fa), ptr(fb_), ptr(sums), ptr(mb) if mb_map else None))
+    return (sums, mb) if mb_map else sums
+
+
+class FrameSsimStruct(ctypes.Structure):
+    """pfv_frame_ssim"""
+    _fields_ = [("q24", ctypes.c_int64 * 3), ("windows", ctypes.c_uint32 * 3), ("ssim", ctypes.c_double * 3), ("ssim_all", ctypes.c_double)]
+
+
+@dataclass
+class FrameSsim:
+    """the structural similarity between the frame one ``Encoder.encode_*`` call was given and its reconstruction"""
+    q24: tuple            # Y, U, V sums of the windows' values in 2^-24 fixed point; zeros for a drop frame
+    windows: tuple        # windows per plane
+    ssim: tuple           # per plane
+    ssim_all: float       # over all windows of the frame
+
+
 class FrameReportStruct(ctypes.Structure):
     """pfv_frame_report"""
     _fields_ = [("type", ctypes.c_int32), ("packet_bytes", ctypes.c_uint32), ("sse", ctypes.c_uint64 * 3), ("psnr", ctypes.c_double * 3),
@@ -48,16 +91,16 @@ class FrameReport:
     psnr_yuv: float
 
 
-def session_distortion(session, call, frames, mb_map: bool, out, out_map):
-    """shared body of EncoderSession.distortion / DecoderSession.distortion: frames (an array -- uploaded -- or a device address) through
+def session_distortion(session, call, frames, mb_map: bool, out, out_map, sum_dtype=np.uint64, map_dtype=np.uint32):
+    """shared body of EncoderSession.distortion / .ssim and DecoderSession.distortion / .ssim: frames (an array -- uploaded -- or a device address) through
     `call` (frames_dev, sse_dev, map_dev); `out` / `out_map` preset the results, so that entries of slots outside the session's window
     come back as they were handed in"""
     ctx = session.ctx
     n, tb = session.n_streams, session.total_blocks
-    sse = np.zeros((n, 3), dtype=np.uint64) if out is None else np.ascontiguousarray(out, dtype=np.uint64).reshape(n, 3).copy()
+    sse = np.zeros((n, 3), dtype=sum_dtype) if out is None else np.ascontiguousarray(out, dtype=sum_dtype).reshape(n, 3).copy()
     mb = None
     if mb_map:
-        mb = np.zeros((n, tb), dtype=np.uint32) if out_map is None else np.ascontiguousarray(out_map, dtype=np.uint32).reshape(n, tb).copy()
+        mb = np.zeros((n, tb), dtype=map_dtype) if out_map is None else np.ascontiguousarray(out_map, dtype=map_dtype).reshape(n, tb).copy()
     bufs = []
     try:
         if isinstance(frames, (int, np.integer)):

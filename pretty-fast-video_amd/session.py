@@ -236,6 +236,19 @@ class EncoderSession(_Geometry):
         from .quality import session_distortion
         return session_distortion(self, self.distortion_dev, frames, mb_map, out, out_map)
 
+    # structural similarity of the same pair of frames (pfv_enc_ssim_dev) ---------------
+    def ssim_dev(self, frames_dev: int, ssim_q24_dev: int, mb_dev: int = 0):
+        """asynchronous on the context's stream; ssim_q24_dev int64 [n_streams][3], mb_dev int32 [n_streams][total_blocks] or 0 (the map
+        then stays in the session's scratch).  Operands, window and stride as distortion_dev."""
+        self.ctx.check(self.ctx._lib.pfv_enc_ssim_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(ssim_q24_dev),
+                                                      ctypes.c_void_p(mb_dev or 0)))
+
+    def ssim(self, frames, mb_map: bool = False, out=None, out_map=None):
+        """SSIM sums per plane in 2^-24 fixed point, int64 [n_streams, 3] (quality.ssim / quality.ssim_windows give the mean); with mb_map
+        also the per-macroblock map int32 [n_streams, total_blocks].  Arguments as distortion."""
+        from .quality import session_distortion
+        return session_distortion(self, self.ssim_dev, frames, mb_map, out, out_map, sum_dtype=np.int64, map_dtype=np.int32)
+
 
 class DecoderSession(_Geometry):
     def __init__(self, ctx: Context, width: int, height: int, qtables, n_streams: int = 1):
@@ -399,3 +412,16 @@ class DecoderSession(_Geometry):
         decoded frames; see EncoderSession.distortion"""
         from .quality import session_distortion
         return session_distortion(self, self.distortion_dev, frames, mb_map, out, out_map)
+
+    # structural similarity of the same pair of frames (pfv_dec_ssim_dev) ---------------
+    def ssim_dev(self, frames_dev: int, ssim_q24_dev: int, mb_dev: int = 0):
+        """asynchronous on the context's stream; ssim_q24_dev int64 [n_streams][3], mb_dev int32 [n_streams][total_blocks] or 0 (the map
+        then stays in the session's scratch).  Operands, window and stride as distortion_dev."""
+        self.ctx.check(self.ctx._lib.pfv_dec_ssim_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(ssim_q24_dev),
+                                                      ctypes.c_void_p(mb_dev or 0)))
+
+    def ssim(self, frames, mb_map: bool = False, out=None, out_map=None):
+        """SSIM sums per plane in 2^-24 fixed point, int64 [n_streams, 3] (quality.ssim / quality.ssim_windows give the mean); with mb_map
+        also the per-macroblock map int32 [n_streams, total_blocks].  Arguments as distortion."""
+        from .quality import session_distortion
+        return session_distortion(self, self.ssim_dev, frames, mb_map, out, out_map, sum_dtype=np.int64, map_dtype=np.int32)

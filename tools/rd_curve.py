@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
 i-frames and p-frames, and the mean PSNR of Y, U, V and of the whole frame.
+
+--ssim adds ssim_y, ssim_u, ssim_v and ssim_all to each line: the mean over the frames of the per-frame structural similarity
+(pfv_encoder_set_frame_ssim: the k_ssim_* kernels on the same pair of frames).  Without the flag the lines are what they were.
+
+--time-ssim (on the GPU box) adds one more line: the k_ssim_mb + k_ssim_sum pair against the k_sse_mb + k_sse_sum pair on the same buffers
+at the benched shape (96 x 1080p, input packed, reconstruction padded, maps to scratch), HIP events around every launch pair, warm-up, the
+MEAN of the samples, the two alternating in three rounds; both times, their ratio and the bytes per second each implies.
 
 --time-kernel (on the GPU box) adds one more line: the k_sse_mb + k_sse_sum pair at the benched shape -- 96 streams of 1920 x 1080,
 input packed, reconstruction padded, map to scratch -- against pfv_dec_get_frame_dev (k_crop_frames) over the same 96 frames, which
@@ -63,11 +70,11 @@ def load():
     return pkg
 
 
-def encode_clip(pkg, ctx, w, h, n_frames, gop, kind, quality, frame_report=True):
-    """-> (stream bytes, reports, seconds per encode call)"""
+def encode_clip(pkg, ctx, w, h, n_frames, gop, kind, quality, frame_report=True, ssim_out=None):
+    """-> (stream bytes, reports, seconds per encode call); ssim_out: a list that receives the FrameSsim of every frame"""
     st = pkg.SyntheticStream(w, h, kind=kind)
     buf = io.BytesIO()
-    enc = pkg.Encoder(buf, w, h, 30, quality, ctx, frame_report=frame_report)
+    enc = pkg.Encoder(buf, w, h, 30, quality, ctx, frame_report=frame_report, frame_ssim=ssim_out is not None)
     reports, secs = [], []
     for t in range(n_frames):
         fr = pkg.VideoFrame.from_packed(w, h, st.frame(t))
@@ -76,21 +83,74 @@ def encode_clip(pkg, ctx, w, h, n_frames, gop, kind, quality, frame_report=True)
         secs.append(time.perf_counter() - t0)
         if frame_report:
             reports.append(enc.last_report)
+        if ssim_out is not None:
+            ssim_out.append(enc.last_ssim)
     enc.finish()
     enc.close()
     return buf.getvalue(), reports, secs
 
 
-def rd_line(pkg, ctx, w, h, n_frames, gop, kind, quality):
-    data, reports, _ = encode_clip(pkg, ctx, w, h, n_frames, gop, kind, quality)
+def rd_line(pkg, ctx, w, h, n_frames, gop, kind, quality, with_ssim=False):
+    ssims = [] if with_ssim else None
+    data, reports, _ = encode_clip(pkg, ctx, w, h, n_frames, gop, kind, quality, ssim_out=ssims)
     by = {1: [r.packet_bytes for r in reports if r.type == 1], 2: [r.packet_bytes for r in reports if r.type == 2]}
     mean = lambda v: float(sum(v) / len(v)) if v else None   # noqa: E731
-    return {"quality": quality, "width": w, "height": h, "frames": n_frames, "gop": gop, "kind": kind,
+    line = {"quality": quality, "width": w, "height": h, "frames": n_frames, "gop": gop, "kind": kind,
             "stream_bytes": len(data), "packet_bytes": sum(r.packet_bytes for r in reports),
             "bytes_per_frame": mean([r.packet_bytes for r in reports]),
             "iframes": len(by[1]), "iframe_bytes_per_frame": mean(by[1]), "pframes": len(by[2]), "pframe_bytes_per_frame": mean(by[2]),
             "psnr_y": mean([r.psnr[0] for r in reports]), "psnr_u": mean([r.psnr[1] for r in reports]),
             "psnr_v": mean([r.psnr[2] for r in reports]), "psnr_yuv": mean([r.psnr_yuv for r in reports])}
+    if with_ssim:
+        line.update({"ssim_y": mean([r.ssim[0] for r in ssims]), "ssim_u": mean([r.ssim[1] for r in ssims]),
+                     "ssim_v": mean([r.ssim[2] for r in ssims]), "ssim_all": mean([r.ssim_all for r in ssims])})
+    return line
+
+
+def time_ssim(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
+    lib = ctx._lib
+    fb = int(lib.pfv_frame_bytes(w, h))
+    tb = int(lib.pfv_total_blocks(w, h))
+    frames = ctx.alloc(fb * n_streams)
+    coef = ctx.alloc(n_streams * tb * 512)
+    sums = ctx.alloc(n_streams * 24)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, frames)
+    enc = pkg.EncoderSession(ctx, w, h, 5, n_streams)
+    enc.encode_iframe_dev(frames, coef)           # prev_frame = the reconstruction of `frames`
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def mean_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.mean(got), min(got), max(got)
+    # alternate the two, so that whatever else the box is doing meets both
+    res = {"ssim": [], "sse": []}
+    for _ in range(3):
+        res["ssim"].append(mean_ms(lambda: enc.ssim_dev(frames, sums)))
+        res["sse"].append(mean_ms(lambda: enc.distortion_dev(frames, sums)))
+    q24 = np.zeros((n_streams, 3), dtype=np.int64)
+    enc.ssim_dev(frames, sums)
+    ctx.download(q24, sums)
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    enc.close()
+    for p in (frames, coef, sums):
+        ctx.free(p)
+    ssim_ms = statistics.mean(m for m, _, _ in res["ssim"])
+    sse_ms = statistics.mean(m for m, _, _ in res["sse"])
+    bytes_moved = n_streams * (fb + int(lib.pfv_padded_frame_bytes(w, h)))     # both operands once; the halo rows and columns are re-reads
+    nw = pkg.ssim_windows(w, h)
+    return {"shape": f"{n_streams} x {w}x{h}", "samples_per_round": samples, "rounds": 3, "ssim_pair_ms": ssim_ms, "sse_pair_ms": sse_ms,
+            "ratio": ssim_ms / sse_ms, "ssim_rounds_ms": res["ssim"], "sse_rounds_ms": res["sse"], "operand_bytes_per_launch": bytes_moved,
+            "ssim_GBps": bytes_moved / ssim_ms / 1e6, "sse_GBps": bytes_moved / sse_ms / 1e6,
+            "ssim_all_stream0": pkg.ssim(int(q24[0].sum()), sum(nw))}
 
 
 def time_kernels(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
@@ -600,12 +660,16 @@ def main():
     ap.add_argument("--probe-p", action="store_true")
     ap.add_argument("--probe-rd", action="store_true")
     ap.add_argument("--probe-p-rd", action="store_true")
+    ap.add_argument("--ssim", action="store_true")
+    ap.add_argument("--time-ssim", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
     with pkg.Context(0) as ctx:
         for q in [int(x) for x in a.qualities.split(",") if x != ""]:
-            print(json.dumps(rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q)), flush=True)
+            print(json.dumps(rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, with_ssim=a.ssim)), flush=True)
+        if a.time_ssim:
+            print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
         if a.probe:
