@@ -118,6 +118,19 @@ struct FrameSsim {
     double ssim_all = 0;             // over all windows of the frame
 };
 
+// out-of-loop deblocking (pfv_hip_ext.h, "out-of-loop deblocking"): the modes of Decoder::set_deblock, the automatic strength of a q-table
+// (min(12, q[0] >> 1)), and the filter on packed Y|U|V frames in host memory at the strengths (Y, U, V), each 0..12
+enum class Deblock { Off = PFV_DEBLOCK_OFF, Auto = PFV_DEBLOCK_AUTO, Fixed = PFV_DEBLOCK_FIXED };
+inline int deblock_strength(const int32_t qtable[64]) { return pfv_deblock_strength(qtable); }
+inline std::vector<uint8_t> frames_deblock(Context &ctx, size_t width, size_t height, const std::vector<uint8_t> &frames, const std::array<uint8_t, 3> &strength)
+{
+    const size_t fb = pfv_frame_bytes((int)width, (int)height);
+    if (!fb || frames.empty() || frames.size() % fb) throw std::invalid_argument("frames_deblock: frames must hold whole packed frames");
+    std::vector<uint8_t> out(frames.size());
+    ctx.check(pfv_frames_deblock(ctx.handle(), (int)width, (int)height, (int)(frames.size() / fb), frames.data(), out.data(), strength.data()));
+    return out;
+}
+
 // src/enc.rs:12-188
 class Encoder {
   public:
@@ -303,6 +316,9 @@ class Decoder {
     uint32_t framerate() const { return (uint32_t)pfv_decoder_framerate(h_); }  // :144-146
     void reset() { ctx_.check(pfv_decoder_reset(h_)); }                         // :148-152
     void set_lookahead(int n_threads) { ctx_.check(pfv_decoder_set_lookahead(h_, n_threads)); }
+    // out-of-loop deblocking of the frames onvideo receives: Auto takes the strengths from the q-tables each packet names, Fixed the ones given;
+    // what the next p-frame predicts from is untouched
+    void set_deblock(Deblock mode, const std::array<uint8_t, 3> &strength = {0, 0, 0}) { ctx_.check(pfv_decoder_set_deblock(h_, (int)mode, strength.data())); }
 
     // false at the end of the stream (Ok(false)), true otherwise; onvideo is called for every decoded frame
     bool advance_delta(double delta, const OnVideo &onvideo)                    // src/dec.rs:154-167

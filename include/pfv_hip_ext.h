@@ -356,6 +356,53 @@ PFV_API int pfv_encoder_set_frame_ssim(pfv_encoder *e, int on);                 
 /* of the last encode_* call; PFV_ERR_STATE when the switch is off, no frame has been encoded, or that call failed */
 PFV_API int pfv_encoder_frame_ssim(pfv_encoder *e, pfv_frame_ssim *out);
 
+/* ------------------------------------------------------------------ out-of-loop deblocking  [B]
+ * The format has no loop filter: the frames shown are the bare 8 x 8-block reconstruction, and the coarse rungs of a ladder block visibly.
+ * This is a POST-filter: it runs on the frame that is displayed and never on the framebuffer the next p-frame predicts from, so streams,
+ * decoder state and every parity with the reference stay bit for bit what they are.  Off by default.
+ *
+ * The filter (normative) works per plane of w x h 8-bit samples, each plane on its own, in integers only.  S is the plane's strength,
+ * 0 .. 12.  S = 0 copies the plane.  One edge takes four samples in a line across it, A B | C D; the edge lies between B and C:
+ *     tdiv(a, n)  = division truncating toward zero (NOT an arithmetic shift: a may be negative)
+ *     d   = tdiv(A - 4B + 4C - D, 8)
+ *     d1  = sign(d) * max(0, |d| - max(0, 2 * (|d| - S)))     ramps up to S, back to 0 at 2S: a real edge is left alone
+ *     d2  = clamp(tdiv(A - D, 4), -(|d1| >> 1), |d1| >> 1)
+ *     B'  = clamp(B + d1, 0, 255)     C' = clamp(C - d1, 0, 255)     A' = A - d2     D' = D + d2
+ * A' and D' need no clamp: they move toward each other by at most |A - D| / 4.
+ *   Stage 1, vertical edges.    For every row y < h and every x with x % 8 == 0, x >= 8 and x + 1 < w, apply the edge with A,B,C,D = samples
+ *                               x-2, x-1, x, x+1 of the input row.
+ *   Stage 2, horizontal edges.  For every column x < w and every y with y % 8 == 0, y >= 8 and y + 1 < h, apply the edge to rows y-2, y-1, y,
+ *                               y+1 of the STAGE-1 RESULT.
+ * Edges within a stage touch disjoint samples (they are 8 apart and each reaches +-2), so each stage is order-free and the result does not
+ * depend on the launch shape.  Samples outside w x h never take part -- the padding of a padded operand included.  The grid is the transform
+ * grid of each plane: 8 x 8 in luma and in each chroma plane at its own resolution; motion-compensated edges off the grid are not searched
+ * for.
+ * The automatic strength of a plane comes from its q-table: S = min(12, q[0] >> 1), q[0] being the DC quantiser (index 0 in raster and in
+ * zigzag order alike; 0 .. 65535, decoders accept hostile tables).  That is 0 at quality 0 and 1 / 2 / 5 for intra luma at qualities
+ * 2 / 5 / 10, and twice that for chroma and for inter tables, whose error is about twice as large.
+ * One launch, k_deblock (csrc/pfv_deblock_kernels.hip); no atomics, nothing allocated: a call is one kernel node of a recorded graph.
+ * Measured on one MI355X, 96 x 1080p: see profiles/deblock.md. */
+PFV_API int pfv_deblock_strength(const int32_t qtable[64]);
+/* src: n_streams frames, PACKED or PADDED (pfv_frames_sse_dev), src_stride bytes apart (0 = back to back in its layout); dst: PACKED frames
+ * dst_stride bytes apart (0 = back to back).  Every byte of the n_streams pictures is written, no byte between or beyond them.
+ * strength: per plane (Y, U, V).  Asynchronous on the context's stream.  PFV_ERR_BAD_ARG for a strength above 12, a null buffer, a
+ * destination stride below pfv_frame_bytes, or source and destination ranges that overlap: in-place is not supported. */
+PFV_API int pfv_frames_deblock_dev(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src_dev, int src_layout, size_t src_stride,
+                                   uint8_t *dst_dev, size_t dst_stride, const uint8_t strength[3]);
+/* host buffers, PACKED on both sides; synchronises */
+PFV_API int pfv_frames_deblock(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src, uint8_t *dst, const uint8_t strength[3]);
+/* A decoder session's switch.  AUTO: per plane, pfv_deblock_strength of the table that the LAST decode call's qidx named (`strength` is
+ * ignored, may be NULL; before the first decode call the strengths are 0); FIXED: `strength`.  While on, every way a frame leaves the session is the filtered picture -- pfv_dec_get_frame,
+ * pfv_dec_get_frame_dev and the output set by pfv_dec_set_output_dev / _strided_dev -- produced by one k_deblock from the current
+ * framebuffer, honouring the window and the output stride; the decode kernels are then launched without their fused crop and k_crop_frames
+ * is not launched.  The framebuffer, the ping-pong, pfv_dec_framebuffer, pfv_dec_distortion_dev and pfv_dec_ssim_dev are untouched (the
+ * latter two keep comparing against the framebuffer).  With mode OFF every launch is exactly what it is without this switch.
+ * pfv_gop_decoder and pfv_batch_decoder drive their sessions' fields directly and stay without the switch. */
+enum { PFV_DEBLOCK_OFF = 0, PFV_DEBLOCK_AUTO = 1, PFV_DEBLOCK_FIXED = 2 };
+PFV_API int pfv_dec_set_deblock(pfv_dec_session *s, int mode, const uint8_t strength[3]);
+/* pfv_decoder: forwards to its session; the callback then receives filtered frames, on the host and on the device output path */
+PFV_API int pfv_decoder_set_deblock(pfv_decoder *d, int mode, const uint8_t strength[3]);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

@@ -36,6 +36,7 @@ PFV_OPT_ENTDEC_LANE_BITS, PFV_OPT_ENTDEC_LAUNCHES, PFV_OPT_ENTDEC_INNER_ROUNDS =
 PFV_ENTROPY_DECODE_AUTO, PFV_ENTROPY_DECODE_HOST, PFV_ENTROPY_DECODE_DEVICE = 0, 1, 2
 PFV_ENC_TRANSFORM_AUTO, PFV_ENC_TRANSFORM_INT = 0, 1
 PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_frames_sse_dev
+PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_deblock / pfv_decoder_set_deblock
 
 
 class PfvError(RuntimeError):
@@ -165,6 +166,11 @@ SIGNATURES = [
     ("pfv_dec_ssim_dev", c_int, [_P, _P, _P, _P]),
     ("pfv_encoder_set_frame_ssim", c_int, [_P, c_int]),
     ("pfv_encoder_frame_ssim", c_int, [_P, _P]),
+    ("pfv_deblock_strength", c_int, [_P]),
+    ("pfv_frames_deblock_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, _P, c_size_t, _P]),
+    ("pfv_frames_deblock", c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
+    ("pfv_dec_set_deblock", c_int, [_P, c_int, _P]),
+    ("pfv_decoder_set_deblock", c_int, [_P, c_int, _P]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

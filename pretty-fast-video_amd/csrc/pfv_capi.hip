@@ -15,6 +15,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #endif
 #include "pfv_quality_kernels.hip"
 #include "pfv_ssim_kernels.hip"
+#include "pfv_deblock_kernels.hip"
 #include "pfv_entropy_kernels.hip"
 #include "pfv_probe_kernels.hip"
 #include "pfv_rdprobe_kernels.hip"
@@ -74,6 +75,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_sessions.hip"
 #include "pfv_quality.hip"
 #include "pfv_ssim.hip"
+#include "pfv_deblock.hip"
 #include "pfv_probe.hip"
 #include "pfv_rdprobe.hip"
 #include "pfv_pprobe.hip"

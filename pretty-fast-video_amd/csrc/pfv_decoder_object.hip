@@ -247,6 +247,12 @@ PFV_API int pfv_decoder_set_output_device(pfv_decoder *d, int on)
     if (!on && d->frame_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(d->frame_dev); d->frame_dev = nullptr; }
     return PFV_OK;
 }
+// out-of-loop deblocking of the frames the callback receives: the session's switch (both output paths fetch the frame from the session)
+PFV_API int pfv_decoder_set_deblock(pfv_decoder *d, int mode, const uint8_t strength[3])
+{
+    if (!d) return fail(nullptr, PFV_ERR_BAD_ARG, "null decoder");
+    return pfv_dec_set_deblock(d->hot, mode, strength);
+}
 PFV_API void pfv_decoder_entropy_counts(const pfv_decoder *d, long counts_out[2])
 {
     if (!d || !counts_out) return;

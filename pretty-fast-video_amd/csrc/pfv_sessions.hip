@@ -163,8 +163,13 @@ struct pfv_dec_session {
     size_t st_sparse_cap = 0;
     uint32_t *q_map = nullptr;               // distortion (pfv_quality.hip): the macroblock map when the caller passes none
     int32_t *ssim_map = nullptr;             // structural similarity (pfv_ssim.hip): the same
+    int db_mode = 0;                         // out-of-loop deblocking of the frames that leave the session (pfv_deblock.hip): PFV_DEBLOCK_*
+    uint8_t db_fixed[3] = {0, 0, 0};         // PFV_DEBLOCK_FIXED: the strengths
+    uint8_t db_auto[3] = {0, 0, 0};          // PFV_DEBLOCK_AUTO: pfv_deblock_strength of the tables the last decode call's qidx named
+    std::vector<uint8_t> db_table;           // pfv_deblock_strength per q-table of the session
 };
 static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
+static int dec_deblock_win(pfv_dec_session *s, int first, int count, uint8_t *frames_out_dev, size_t out_stride);   // pfv_deblock.hip
 static int enc_ssim_enqueue(pfv_enc_session *s);     // pfv_ssim.hip
 
 extern "C" {
@@ -669,6 +674,8 @@ PFV_API int pfv_dec_session_create(pfv_ctx *ctx, int width, int height, const in
     s->win_count = n_streams;
     s->lane_mapping = ctx->opt_lane_mapping;
     s->geom = frame_geom(width, height, n_streams);
+    s->db_table.resize((size_t)n_dev);
+    for (int i = 0; i < n_dev; i++) s->db_table[(size_t)i] = (uint8_t)pfv_deblock_strength(qtables + (size_t)i * 64);
     size_t pad_bytes = (size_t)s->geom.pad_frame_bytes * n_streams;
     hipError_t e = hipMalloc((void **)&s->qtab_dev, tabs.size() * sizeof(QTab));
     if (e == hipSuccess) e = hipMemcpy(s->qtab_dev, tabs.data(), tabs.size() * sizeof(QTab), hipMemcpyHostToDevice);
@@ -766,7 +773,7 @@ static int dec_launch(pfv_dec_session *s, bool pframe, int first, int count, con
     if (rc) return rc;
     const size_t ostride = s->out_stride ? s->out_stride : (size_t)s->geom.src_frame_bytes;
     const size_t mb0 = (size_t)first * (size_t)s->geom.mbs_per_frame, pad0 = (size_t)first * (size_t)s->geom.pad_frame_bytes;
-    const bool fused = fused_output_ok(s);
+    const bool fused = !s->db_mode && fused_output_ok(s);   // a deblocked output is written by k_deblock alone
     uint8_t *crop = fused ? s->frames_out + (size_t)first * ostride : nullptr;
     g = dec_out_geom(s, g, s->frames_out);
     g.n_streams = count;
@@ -791,6 +798,8 @@ static int dec_step(pfv_dec_session *s, bool pframe, const int8_t *mv_dev, const
     int rc = dec_launch(s, pframe, s->win_first, s->win_count, mv_dev, has_coef_dev, coefs, qidx);
     if (rc) return rc;
     s->cur ^= 1;
+    for (int i = 0; i < 3; i++) s->db_auto[i] = s->db_table[qidx[i]];   // dec_geom has checked the indices; a u8 names one of the first 256 tables
+    if (s->frames_out && s->db_mode) return dec_deblock_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
     if (s->frames_out && !fused_output_ok(s)) return dec_crop_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
     return PFV_OK;
 }
@@ -997,6 +1006,7 @@ PFV_API int pfv_dec_get_frame_dev(pfv_dec_session *s, uint8_t *frames_out_dev)
     pfv_ctx *ctx = s->ctx;
     if (!frames_out_dev) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_dec_get_frame_dev: null buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (s->db_mode) return dec_deblock_win(s, 0, s->n_streams, frames_out_dev, 0);
     return dec_crop_win(s, 0, s->n_streams, frames_out_dev, 0);
 }
 

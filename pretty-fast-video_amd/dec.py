@@ -52,6 +52,13 @@ class Decoder:
         self.ctx.check(self.ctx._lib.pfv_decoder_set_output_device(self.handle, 1 if on else 0))
         self._device_out = bool(on)
 
+    def set_deblock(self, mode=None, strength=None):
+        """out-of-loop deblocking of the frames ``onvideo`` receives, on the host and on the device output path: "off", "auto" (strengths
+        from the q-tables each packet names) or "fixed" with strength = (Y, U, V), each 0..12 (pfv_decoder_set_deblock)"""
+        from .quality import deblock_args
+        m, p, _keep = deblock_args(mode, strength)
+        self.ctx.check(self.ctx._lib.pfv_decoder_set_deblock(self.handle, m, p))
+
     def entropy_counts(self) -> dict:
         """packets whose run streams the device read / that its stage left to the host parser (pfv_decoder_entropy_counts)"""
         a = (ctypes.c_long * 2)()

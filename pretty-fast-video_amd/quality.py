@@ -1,6 +1,6 @@
 """Distortion measured on the device (include/pfv_hip_ext.h, "distortion on the device"): squared error per plane and per
 macroblock between frames, PSNR, and the frame report of :class:`Encoder`; and structural similarity ("structural similarity on the
-device"): the SSIM sums per plane and per macroblock in 2^-24 fixed point, the mean from them, and the frame SSIM of :class:`Encoder`.
+device"): the SSIM sums per plane and per macroblock in 2^-24 fixed point, the mean from them, and the frame SSIM of :class:`Encoder`; and the out-of-loop deblocking filter of the frames that are shown (k_deblock).
 The sums come from the k_sse_* and k_ssim_* kernels (csrc/pfv_quality_kernels.hip, csrc/pfv_ssim_kernels.hip); this module only marshals.
 """
 from __future__ import annotations
@@ -59,6 +59,38 @@ def frames_ssim(ctx: Context, width: int, height: int, a, b, mb_map: bool = Fals
     mb = np.zeros((n, int(ctx._lib.pfv_total_blocks(int(width), int(height)))), dtype=np.int32) if mb_map else None
     ctx.check(ctx._lib.pfv_frames_ssim(ctx.handle, int(width), int(height), n, ptr(fa), ptr(fb_), ptr(sums), ptr(mb) if mb_map else None))
     return (sums, mb) if mb_map else sums
+
+
+DEBLOCK_MODES = {"off": _lib.PFV_DEBLOCK_OFF, "auto": _lib.PFV_DEBLOCK_AUTO, "fixed": _lib.PFV_DEBLOCK_FIXED}
+
+
+def deblock_args(mode, strength):
+    """(mode, strength pointer) of pfv_dec_set_deblock / pfv_decoder_set_deblock: mode "off" / "auto" / "fixed" or a PFV_DEBLOCK_* value;
+    giving strengths alone means "fixed".  The array is returned as well: it must outlive the call."""
+    if mode is None:
+        mode = "fixed" if strength is not None else "auto"
+    m = DEBLOCK_MODES[mode] if isinstance(mode, str) else int(mode)
+    st = None if strength is None else np.ascontiguousarray(strength, dtype=np.uint8).reshape(3)
+    return m, (ptr(st) if st is not None else None), st
+
+
+def deblock_strength(qtable) -> int:
+    """the automatic deblocking strength of a q-table, min(12, q[0] >> 1) (pfv_deblock_strength)"""
+    q = np.ascontiguousarray(qtable, dtype=np.int32).reshape(64)
+    return int(_lib.load().pfv_deblock_strength(ptr(q)))
+
+
+def frames_deblock(ctx: Context, width: int, height: int, frames, strength) -> np.ndarray:
+    """the out-of-loop deblocking filter (include/pfv_hip_ext.h, "out-of-loop deblocking") on packed Y|U|V frames (uint8, n frames) at the
+    strengths (Y, U, V), each 0..12: uint8 [n, frame_bytes] (pfv_frames_deblock)"""
+    fb = int(ctx._lib.pfv_frame_bytes(int(width), int(height)))
+    f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    assert fb > 0 and f.size % fb == 0 and f.size
+    n = f.size // fb
+    st = np.ascontiguousarray(strength, dtype=np.uint8).reshape(3)
+    out = np.empty((n, fb), dtype=np.uint8)
+    ctx.check(ctx._lib.pfv_frames_deblock(ctx.handle, int(width), int(height), n, ptr(f), ptr(out), ptr(st)))
+    return out
 
 
 class FrameSsimStruct(ctypes.Structure):

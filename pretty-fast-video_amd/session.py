@@ -397,6 +397,14 @@ class DecoderSession(_Geometry):
     def get_frame_dev(self, frames_dev: int):
         self.ctx.check(self.ctx._lib.pfv_dec_get_frame_dev(self.handle, ctypes.c_void_p(frames_dev)))
 
+    def set_deblock(self, mode=None, strength=None):
+        """out-of-loop deblocking of every frame that leaves the session (get_frame, get_frame_dev, the output buffer): "off", "auto"
+        (strengths from the q-tables the last decode call named) or "fixed" with strength = (Y, U, V), each 0..12.  The framebuffer and
+        what the next p-frame predicts from are untouched (pfv_dec_set_deblock)."""
+        from .quality import deblock_args
+        m, p, _keep = deblock_args(mode, strength)
+        self.ctx.check(self.ctx._lib.pfv_dec_set_deblock(self.handle, m, p))
+
     def framebuffer(self) -> np.ndarray:
         out = np.empty((self.n_streams, self.padded_frame_bytes), dtype=np.uint8)
         self.ctx.check(self.ctx._lib.pfv_dec_framebuffer(self.handle, ptr(out)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -13,6 +13,15 @@ i-frames and p-frames, and the mean PSNR of Y, U, V and of the whole frame.
 --time-ssim (on the GPU box) adds one more line: the k_ssim_mb + k_ssim_sum pair against the k_sse_mb + k_sse_sum pair on the same buffers
 at the benched shape (96 x 1080p, input packed, reconstruction padded, maps to scratch), HIP events around every launch pair, warm-up, the
 MEAN of the samples, the two alternating in three rounds; both times, their ratio and the bytes per second each implies.
+
+--deblock adds, per quality, the PSNR and SSIM of the DEBLOCKED reconstruction (db_psnr_*, db_ssim_*) next to the plain ones (psnr_*, ssim_*),
+and the strengths used (db_strength_i / _p): an encoder session's prev_frame as PADDED source -> pfv_frames_deblock_dev at the automatic
+strengths (pfv_deblock_strength) of the frame's tables -> pfv_frames_sse_dev / pfv_frames_ssim_dev against the input.  --dump DIR writes
+what was measured as raw packed frames: q<quality>_input.yuv, q<quality>_recon.yuv (prev_frame cropped), q<quality>_deblocked.yuv.
+
+--time-deblock (on the GPU box) adds one more line: k_deblock against k_crop_frames on the same 96 x 1080p launch -- pfv_dec_get_frame_dev of
+one decoder session with the switch fixed at (5, 10, 10), at (0, 0, 0) (the copy path) and off -- HIP events around every launch, warm-up, the
+median of the samples, alternating in three rounds; and pfv_dec_pframe_dev with an output buffer set, switch off (fused crop) against auto.
 
 --time-kernel (on the GPU box) adds one more line: the k_sse_mb + k_sse_sum pair at the benched shape -- 96 streams of 1920 x 1080,
 input packed, reconstruction padded, map to scratch -- against pfv_dec_get_frame_dev (k_crop_frames) over the same 96 frames, which
@@ -151,6 +160,121 @@ def time_ssim(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
             "ratio": ssim_ms / sse_ms, "ssim_rounds_ms": res["ssim"], "sse_rounds_ms": res["sse"], "operand_bytes_per_launch": bytes_moved,
             "ssim_GBps": bytes_moved / ssim_ms / 1e6, "sse_GBps": bytes_moved / sse_ms / 1e6,
             "ssim_all_stream0": pkg.ssim(int(q24[0].sum()), sum(nw))}
+
+
+def deblock_line(pkg, ctx, w, h, n_frames, gop, kind, quality, dump=None):
+    """the keys --deblock adds to a quality's line"""
+    lib = ctx._lib
+    P = ctypes.c_void_p
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    tabs = pkg.qtables_from_quality(quality)[:4]
+    s = [pkg.deblock_strength(t) for t in tabs]
+    strength = {True: np.array([s[0], s[1], s[1]], np.uint8), False: np.array([s[2], s[3], s[3]], np.uint8)}     # i-frame / p-frame tables
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    enc = pkg.EncoderSession(ctx, w, h, quality, 1)
+    bufs = [ctx.alloc(n) for n in (fb, tb * 512, tb * 2, tb, fb, 24, 24)]
+    frame_d, coef_d, mv_d, has_d, out_d, sse_d, ssim_d = bufs
+    nw = pkg.ssim_windows(w, h)
+    dims = [(w, h), (w // 2, h // 2), (w // 2, h // 2)]
+    rows = {"plain": [], "db": []}
+    dumped = {"input": [], "recon": [], "deblocked": []}
+    try:
+        for t in range(n_frames):
+            f = st.frame(t)
+            ctx.upload(frame_d, f)
+            intra = t % gop == 0
+            if intra:
+                enc.encode_iframe_dev(frame_d, coef_d)
+            else:
+                enc.encode_pframe_dev(frame_d, mv_d, has_d, coef_d)
+            prev = lib.pfv_enc_prev_frame_dev(enc.handle, 0)
+            ctx.check(lib.pfv_frames_deblock_dev(ctx.handle, w, h, 1, P(prev), pkg._lib.PFV_FRAME_PADDED, 0, P(out_d), 0, strength[intra].ctypes.data_as(P)))
+            for key, b_dev, layout in (("plain", prev, pkg._lib.PFV_FRAME_PADDED), ("db", out_d, pkg._lib.PFV_FRAME_PACKED)):
+                ctx.check(lib.pfv_frames_sse_dev(ctx.handle, w, h, 1, P(frame_d), pkg._lib.PFV_FRAME_PACKED, 0, P(b_dev), layout, 0, P(sse_d), None))
+                ctx.check(lib.pfv_frames_ssim_dev(ctx.handle, w, h, 1, P(frame_d), pkg._lib.PFV_FRAME_PACKED, 0, P(b_dev), layout, 0, P(ssim_d), None))
+                sse, q24 = np.zeros(3, np.uint64), np.zeros(3, np.int64)
+                ctx.download(sse, sse_d)
+                ctx.download(q24, ssim_d)
+                rows[key].append([pkg.psnr(int(sse[i]), dims[i][0] * dims[i][1]) for i in range(3)] + [pkg.psnr(int(sse.sum()), fb)] +
+                                 [pkg.ssim(int(q24[i]), nw[i]) for i in range(3)] + [pkg.ssim(int(q24.sum()), sum(nw))])
+            if dump:
+                got = np.zeros(fb, np.uint8)
+                ctx.download(got, out_d)
+                pad = enc.prev_frame()[0]
+                parts, off = [], 0
+                for pw, ph in dims:
+                    sw, sh = (pw + 15) // 16 * 16, (ph + 15) // 16 * 16
+                    parts.append(pad[off:off + sw * sh].reshape(sh, sw)[:ph, :pw].reshape(-1))
+                    off += sw * sh
+                dumped["input"].append(f); dumped["recon"].append(np.concatenate(parts)); dumped["deblocked"].append(got)
+    finally:
+        enc.close()
+        for b in bufs:
+            ctx.free(b)
+    if dump:
+        os.makedirs(dump, exist_ok=True)
+        for name, frames in dumped.items():
+            np.concatenate(frames).tofile(os.path.join(dump, f"q{quality}_{name}.yuv"))
+    names = ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv", "ssim_y", "ssim_u", "ssim_v", "ssim_all")
+    line = {"db_strength_i": [int(v) for v in strength[True]], "db_strength_p": [int(v) for v in strength[False]]}
+    for k, name in enumerate(names):
+        if name.startswith("ssim"):
+            line[name] = float(sum(r[k] for r in rows["plain"]) / len(rows["plain"]))
+        line["db_" + name] = float(sum(r[k] for r in rows["db"]) / len(rows["db"]))
+    return line
+
+
+def time_deblock(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
+    lib = ctx._lib
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    f0, f1, out = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    enc = pkg.EncoderSession(ctx, w, h, 10, n_streams)
+    dec = pkg.DecoderSession(ctx, w, h, np.stack(pkg.qtables_from_quality(10)[:4]), n_streams)
+    enc.encode_iframe_dev(f0, coef)
+    dec.decode_iframe_dev(coef)                   # framebuffer = frame 0 at quality 10: the blocking the filter is for
+    enc.encode_pframe_dev(f1, mv, has, coef)
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got), min(got), max(got)
+    modes = {"deblock": ("fixed", (5, 10, 10)), "deblock_s0": ("fixed", (0, 0, 0)), "crop": ("off", None)}
+    res = {k: [] for k in modes}
+    for _ in range(3):                            # alternate, so that whatever else the box is doing meets all of them
+        for key, (mode, st) in modes.items():
+            dec.set_deblock(mode, st)
+            res[key].append(median_ms(lambda: dec.get_frame_dev(out)))
+    loop = {"off": [], "auto": []}
+    dec.set_output_dev(out)
+    for _ in range(3):
+        for mode in loop:
+            dec.set_deblock(mode)
+            loop[mode].append(median_ms(lambda: dec.decode_pframe_dev(mv, has, coef)))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    enc.close(); dec.close()
+    for p in (f0, f1, out, coef, mv, has):
+        ctx.free(p)
+    med = {k: statistics.median(m for m, _, _ in v) for k, v in res.items()}
+    bytes_moved = n_streams * (fb + int(lib.pfv_padded_frame_bytes(w, h)))
+    return {"shape": f"{n_streams} x {w}x{h}", "samples_per_round": samples, "rounds": 3, "deblock_ms": med["deblock"], "deblock_s0_ms": med["deblock_s0"],
+            "crop_ms": med["crop"], "ratio": med["deblock"] / med["crop"], "ratio_s0": med["deblock_s0"] / med["crop"], "rounds_ms": res,
+            "bytes_per_launch": bytes_moved, "deblock_GBps": bytes_moved / med["deblock"] / 1e6, "crop_GBps": bytes_moved / med["crop"] / 1e6,
+            "dec_pframe_plus_output_off_ms": statistics.median(m for m, _, _ in loop["off"]),
+            "dec_pframe_plus_output_auto_ms": statistics.median(m for m, _, _ in loop["auto"]), "dec_pframe_rounds_ms": loop}
 
 
 def time_kernels(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
@@ -662,14 +786,22 @@ def main():
     ap.add_argument("--probe-p-rd", action="store_true")
     ap.add_argument("--ssim", action="store_true")
     ap.add_argument("--time-ssim", action="store_true")
+    ap.add_argument("--deblock", action="store_true")
+    ap.add_argument("--dump", default=None)
+    ap.add_argument("--time-deblock", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
     with pkg.Context(0) as ctx:
         for q in [int(x) for x in a.qualities.split(",") if x != ""]:
-            print(json.dumps(rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, with_ssim=a.ssim)), flush=True)
+            line = rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, with_ssim=a.ssim)
+            if a.deblock:
+                line.update(deblock_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, dump=a.dump))
+            print(json.dumps(line), flush=True)
         if a.time_ssim:
             print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
+        if a.time_deblock:
+            print(json.dumps({"time_deblock": time_deblock(pkg, ctx)}), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
         if a.probe:
