@@ -237,6 +237,30 @@ class Encoder {
     // bytes, else the one with the smallest squared error; encode_frame then weighs the p-frame against the i-frame by the same measure
     // (pfv_encoder_set_pframe_quality_floor)
     void set_pframe_quality_floor(double min_psnr_yuv) { ctx_.check(pfv_encoder_set_pframe_quality_floor(h_, min_psnr_yuv)); }
+    // ... and the SSIM sums per plane at every rung, q24[3 * r + plane], as pfv_frame_ssim.q24 of a frame written at that rung
+    // (pfv_encoder_probe_iframe_ssim / pfv_encoder_probe_pframe_ssim)
+    std::vector<uint32_t> probe_iframe_ssim(const VideoFrame &f, std::vector<uint64_t> &sse, std::vector<int64_t> &q24) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        sse.assign(3 * sizes.size(), 0);
+        q24.assign(3 * sizes.size(), 0);
+        ctx_.check(pfv_encoder_probe_iframe_ssim(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data(), sse.data(), q24.data()));
+        return sizes;
+    }
+    std::vector<uint32_t> probe_pframe_ssim(const VideoFrame &f, std::vector<uint64_t> &sse, std::vector<int64_t> &q24) const
+    {
+        check_frame(f);
+        std::vector<uint32_t> sizes((size_t)n_rungs());
+        sse.assign(3 * sizes.size(), 0);
+        q24.assign(3 * sizes.size(), 0);
+        ctx_.check(pfv_encoder_probe_pframe_ssim(h_, f.plane_y.pixels.data(), f.plane_u.pixels.data(), f.plane_v.pixels.data(), sizes.data(), sse.data(), q24.data()));
+        return sizes;
+    }
+    // floors on the frame's mean SSIM, 0 = off, (0, 1]: of the rungs within the budget that reach this floor and the PSNR floor the one with
+    // the fewest bytes, else the one with the largest SSIM (pfv_encoder_set_iframe_ssim_floor / pfv_encoder_set_pframe_ssim_floor)
+    void set_iframe_ssim_floor(double min_ssim) { ctx_.check(pfv_encoder_set_iframe_ssim_floor(h_, min_ssim)); }
+    void set_pframe_ssim_floor(double min_ssim) { ctx_.check(pfv_encoder_set_pframe_ssim_floor(h_, min_ssim)); }
     // on, with a set_rate budget and more than one rung: encode_pframe takes the finest rung whose probed payload fits, the coarsest if none does
     void set_pframe_probe(bool on) { ctx_.check(pfv_encoder_set_pframe_probe(h_, on ? 1 : 0)); }
     // encode_frame forces an i-frame once max_interval frames (drop frames included) have followed the last one; 0 = never

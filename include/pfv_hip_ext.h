@@ -545,6 +545,55 @@ PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const 
  * one download of 28 * n_rungs bytes and one synchronisation per p-frame; the frame goes up once. */
 PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr_yuv);
 
+/* ------------------------------------------------------------------ SSIM probe, i- and p-frame SSIM floors  [B]
+ * Squared error rates the blocking of a coarse rung far too kindly, and the two metrics do rank the rungs of this codec differently.  The
+ * SSIM probes are the rate-distortion probes with one more result: per slot of the window and EVERY rung
+ *   sizes_dev, sse_dev, stats_dev   exactly what pfv_enc_probe_iframe_rd_dev / pfv_enc_probe_pframe_rd_dev define (stats_dev may be NULL);
+ *   ssim_q24_dev   int64[n_streams][n_rungs][3] (Y, U, V): per plane the sum of q exactly as pfv_frames_ssim_dev defines it, between the frame
+ *                  and the reconstruction that pfv_enc_iframe_dev / pfv_enc_pframe_dev at that rung would leave in prev_frame (a skipped
+ *                  macroblock reconstructs to its patch).  The window count per plane is pfv_ssim_windows; a plane without windows reports 0.
+ *                  Undefined where the size is 0xffffffff.  The values are the ones pfv_enc_ssim_dev returns behind a real encode at that
+ *                  rung, bit for bit: the same integers through the same window function.
+ * Everything else is the rate-distortion probes' contract: the call changes nothing (prev_frame, the ping-pong index, the current rung),
+ * leaves the entries of slots outside the window alone, honours the frame stride, is asynchronous on the context's stream and recordable
+ * after one unrecorded call (the first call allocates; inside a recording it returns PFV_ERR_STATE); the host-buffer forms work on all
+ * slots, packed, and synchronise.
+ * Three launches (csrc/pfv_ssimprobe_kernels.hip): k_probe_iframe_ssim or k_probe_pframe_ssim leaves the 4 x 4 block sums of every rung in
+ * a map, k_probe_ssim_windows forms every window from its four blocks and writes the plane sums through a fixed reduction, and the RD
+ * probes' own tail (k_probe_rd_sizes / k_pprobe_rd_sizes) stays a launch of its own.  No host-side clear, no host synchronisation.
+ * Scratch: the map takes n_streams * pfv_total_blocks * (n_rungs * 128 + 64) bytes (1080p, 11 rungs: 18 MB per stream), allocated by the
+ * first call, freed with the session. */
+PFV_API int pfv_enc_probe_iframe_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev,
+                                          int64_t *ssim_q24_dev, uint32_t *stats_dev /* may be NULL */);
+PFV_API int pfv_enc_probe_iframe_ssim(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out);   /* host buffers, all slots, packed; synchronises */
+PFV_API int pfv_enc_probe_pframe_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev,
+                                          int64_t *ssim_q24_dev, uint32_t *stats_dev /* may be NULL */);
+PFV_API int pfv_enc_probe_pframe_ssim(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out);   /* host buffers, all slots, packed; synchronises */
+/* pfv_encoder: the same for one frame, as an i-frame or against the encoder's reference; no state changes.  The p-frame form returns
+ * PFV_ERR_STATE when the encoder is poisoned or finished. */
+PFV_API int pfv_encoder_probe_iframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/,
+                                          uint64_t *sse_out /*[n_rungs][3]*/, int64_t *ssim_q24_out /*[n_rungs][3]*/);
+PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out /*[n_rungs]*/,
+                                          uint64_t *sse_out /*[n_rungs][3]*/, int64_t *ssim_q24_out /*[n_rungs][3]*/);
+/* SSIM floors: min_ssim is the mean SSIM of the frame as pfv_frame_ssim.ssim_all defines it.  0 = off (default: today's behaviour, byte for
+ * byte); values in (0, 1] are legal, 1 meaning "the best-looking rung that fits"; NaN, negative values and values above 1 return
+ * PFV_ERR_BAD_ARG.  With a floor of that frame type on and more than one rung, encode_iframe / encode_pframe run the SSIM probe in place of
+ * the size or rate-distortion probe: one launch group, one download of 52 * n_rungs bytes, one synchronisation; the frame goes up once.
+ *   ALLOWED as without it: the rung is encodable and within the i-frame budget / the pfv_encoder_set_rate budget (for p-frames a hard cap;
+ *   the soft rule is not applied); none allowed: the coarsest rung.
+ *   A rung MEETS when it is allowed, meets the PSNR floor of that frame type if one is on, and
+ *   pfv_ssim(q24[Y] + q24[U] + q24[V], windows) >= min_ssim.  A frame without any window meets every SSIM floor.
+ *   Of the rungs that meet, the one with the FEWEST bytes, ties to the lower index.  If none meets and the frame has windows: the allowed
+ *   rung with the largest q24 total, ties to the smaller total squared error, then fewer bytes, then the lower index.  (Without windows the
+ *   PSNR floor's rule decides.)  The chosen rung becomes the current rung.
+ * pfv_encoder_encode_frame with either kind of p-frame floor on takes rule 4 in its floor form: rp is the floors' rung; the i-frame is
+ * measured from the same upload, by the SSIM probe if the i-frame or the p-frame SSIM floor is on; ri is encode_iframe's own choice from
+ * those results; a candidate MEETS by the p-frame floors that are on.  Exactly one meets: that one.  Both: fewer bytes, ties to the i-frame.
+ * Neither, the p-frame SSIM floor on and windows: the larger q24 total, then the smaller squared error, then fewer bytes, then the i-frame;
+ * otherwise neither-meets is the PSNR floor's rule.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have no floors. */
+PFV_API int pfv_encoder_set_iframe_ssim_floor(pfv_encoder *e, double min_ssim);
+PFV_API int pfv_encoder_set_pframe_ssim_floor(pfv_encoder *e, double min_ssim);
+
 /* ------------------------------------------------------------------ batch encoder (n streams per step, pipelined)  [B]
  * n independent streams of one geometry encoded together -- the reference runs one Encoder per stream (src/enc.rs:12-26);
  * every writer receives exactly the bytes an Encoder of its own would have written.  Per frame step: ONE upload of all

@@ -195,6 +195,14 @@ SIGNATURES = [
     ("pfv_enc_probe_pframe_rd", c_int, [_P, _P, _P, _P]),
     ("pfv_encoder_probe_pframe_rd", c_int, [_P, _P, _P, _P, _P, _P]),
     ("pfv_encoder_set_pframe_quality_floor", c_int, [_P, ctypes.c_double]),
+    ("pfv_enc_probe_iframe_ssim_dev", c_int, [_P, _P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_iframe_ssim", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_pframe_ssim_dev", c_int, [_P, _P, _P, _P, _P, _P]),
+    ("pfv_enc_probe_pframe_ssim", c_int, [_P, _P, _P, _P, _P]),
+    ("pfv_encoder_probe_iframe_ssim", c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("pfv_encoder_probe_pframe_ssim", c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("pfv_encoder_set_iframe_ssim_floor", c_int, [_P, ctypes.c_double]),
+    ("pfv_encoder_set_pframe_ssim_floor", c_int, [_P, ctypes.c_double]),
     ("pfv_encoder_set_pframe_probe", c_int, [_P, c_int]),
     ("pfv_encoder_set_gop", c_int, [_P, c_int]),
     ("pfv_encoder_encode_frame", c_int, [_P, _P, _P, _P, _P]),

@@ -21,6 +21,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #include "pfv_rdprobe_kernels.hip"
 #include "pfv_pprobe_kernels.hip"
 #include "pfv_prdprobe_kernels.hip"
+#include "pfv_ssimprobe_kernels.hip"
 #include "pfv_entdec_kernels.hip"
 #include "pfv_synth_kernels.hip"
 #include "pfv_host.hip"
@@ -80,6 +81,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_rdprobe.hip"
 #include "pfv_pprobe.hip"
 #include "pfv_prdprobe.hip"
+#include "pfv_ssimprobe.hip"
 #include "pfv_container.hip"
 #include "pfv_stream_objects.hip"
 #include "pfv_batch_objects.hip"

@@ -123,6 +123,10 @@ struct pfv_enc_session {
     // p-frame rate-distortion probe (pfv_prdprobe.hip): pprobe_acc and rd_acc are its accumulators; of the host-buffer form the sums
     // [n_streams][n_rungs][3], the sizes [n_streams][n_rungs] and the counts [n_streams][n_rungs][kPProbeStats], in this order
     uint64_t *prd_out = nullptr;
+    // SSIM probe (pfv_ssimprobe.hip): the block-sum map, n_streams * mbs_per_frame * (n_rungs * 128 + 64) bytes (probe_acc / pprobe_acc and
+    // rd_acc are its accumulators); of the host-buffer form both sums [n_streams][n_rungs][3], the sizes and the counts, in this order
+    uint32_t *ssim_probe_map = nullptr;
+    uint64_t *ssim_probe_out = nullptr;
     // device entropy stage (pfv_enc_entropy_enable)
     bool ent_on = false;
     uint32_t ent_cap = 0;
@@ -249,7 +253,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)

@@ -86,6 +86,8 @@ struct pfv_encoder {
     uint32_t budget_i = 0;                 // i-frame payload bytes (pfv_encoder_set_iframe_budget); 0: off
     double floor_i = 0.0;                  // i-frame PSNR-YUV floor in dB (pfv_encoder_set_iframe_quality_floor); 0: off
     double floor_p = 0.0;                  // p-frame PSNR-YUV floor in dB (pfv_encoder_set_pframe_quality_floor); 0: off
+    double sfloor_i = 0.0;                 // i-frame floor on the frame's mean SSIM (pfv_encoder_set_iframe_ssim_floor); 0: off
+    double sfloor_p = 0.0;                 // p-frame floor on the frame's mean SSIM (pfv_encoder_set_pframe_ssim_floor); 0: off
     // p-frame size probe (pfv_encoder_set_pframe_probe): the hard p-frame budget; automatic frame types (pfv_encoder_encode_frame)
     bool pprobe_on = false;
     int gop_max = 0;                       // pfv_encoder_set_gop: an i-frame is forced once this many frames have followed the last one; 0: never
@@ -581,8 +583,24 @@ PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr
     e->floor_p = min_psnr_yuv;
     return PFV_OK;
 }
-// the p-frame floor applies: it is set and there is a rung to choose
-static bool pframe_floor(const pfv_encoder *e) { return e->floor_p > 0.0 && e->hot->n_rungs > 1; }
+// SSIM floors on the frame's mean SSIM (pfv_frame_ssim.ssim_all), 0 = off, (0, 1] legal; the rules are at the declarations
+// (include/pfv_hip_ext.h), in ssim_floor_rung and in pfv_encoder_encode_frame
+PFV_API int pfv_encoder_set_iframe_ssim_floor(pfv_encoder *e, double min_ssim)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!(min_ssim >= 0.0 && min_ssim <= 1.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_iframe_ssim_floor: the floor must lie in [0, 1] (NaN is not legal)");
+    e->sfloor_i = min_ssim;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_set_pframe_ssim_floor(pfv_encoder *e, double min_ssim)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!(min_ssim >= 0.0 && min_ssim <= 1.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_ssim_floor: the floor must lie in [0, 1] (NaN is not legal)");
+    e->sfloor_p = min_ssim;
+    return PFV_OK;
+}
+// a p-frame floor of either kind applies: it is set and there is a rung to choose
+static bool pframe_floor(const pfv_encoder *e) { return (e->floor_p > 0.0 || e->sfloor_p > 0.0) && e->hot->n_rungs > 1; }
 
 // the report of the encode_* call that has just written `packet_bytes` bytes (type 3: a drop frame, nothing measured)
 static void fill_ssim(pfv_encoder *e, int type);
@@ -777,6 +795,46 @@ static int floor_rung(const pfv_encoder *e, const uint32_t *sizes, const uint64_
     }
     return meets >= 0 ? meets : best >= 0 ? best : s->n_rungs - 1;
 }
+// windows of the whole frame (pfv_ssim_windows over the three planes)
+static uint64_t frame_windows(const pfv_encoder *e)
+{
+    uint32_t n[3] = {0, 0, 0};
+    (void)pfv_ssim_windows(e->width, e->height, n);
+    return (uint64_t)n[0] + n[1] + n[2];
+}
+// a candidate meets the floors that are on (0: off) with its plane sums of squared error and of q; a frame without windows meets every SSIM floor
+static bool meets_floors(const pfv_encoder *e, const uint64_t *sse, const int64_t *q24, double floor_db, double floor_ssim)
+{
+    if (floor_db > 0.0 && !(pfv_psnr(sse[0] + sse[1] + sse[2], (uint64_t)pfv_frame_bytes(e->width, e->height)) >= floor_db)) return false;
+    const uint64_t windows = frame_windows(e);
+    return !(floor_ssim > 0.0) || windows == 0 || pfv_ssim(q24[0] + q24[1] + q24[2], windows) >= floor_ssim;
+}
+// floor_rung with an SSIM floor beside the PSNR floor (either may be 0: off; with the SSIM floor off it IS floor_rung): sizes, plane sums
+// [n_rungs][3] and SSIM sums [n_rungs][3] of the SSIM probe.  Allowed as there.  Of the allowed rungs that meet both floors the one with the
+// fewest bytes; if none does and the frame has windows, the allowed rung with the largest q24 total, then the smallest squared error, then
+// the fewest bytes; ties to the lower index.  Without windows the SSIM floor is met by every rung and floor_rung's answer holds.
+static int ssim_floor_rung(const pfv_encoder *e, const uint32_t *sizes, const uint64_t *sse, const int64_t *q24, uint32_t budget, double floor_db, double floor_ssim)
+{
+    const pfv_enc_session *s = e->hot;
+    if (!(floor_ssim > 0.0) || frame_windows(e) == 0) {
+        if (floor_db > 0.0) return floor_rung(e, sizes, sse, budget, floor_db);
+        int meets = -1;   // no floor decides: the fewest bytes of the allowed rungs
+        for (int r = 0; r < s->n_rungs; r++)
+            if (sizes[r] != kEntErrOversize && !(budget && sizes[r] > budget) && (meets < 0 || sizes[r] < sizes[meets])) meets = r;
+        return meets >= 0 ? meets : s->n_rungs - 1;
+    }
+    int meets = -1, best = -1;
+    int64_t best_q = 0;
+    uint64_t best_sse = 0;
+    for (int r = 0; r < s->n_rungs; r++) {
+        if (sizes[r] == kEntErrOversize || (budget && sizes[r] > budget)) continue;
+        const uint64_t total = sse[3 * r] + sse[3 * r + 1] + sse[3 * r + 2];
+        const int64_t q = q24[3 * r] + q24[3 * r + 1] + q24[3 * r + 2];
+        if (meets_floors(e, sse + 3 * r, q24 + 3 * r, floor_db, floor_ssim) && (meets < 0 || sizes[r] < sizes[meets])) meets = r;
+        if (best < 0 || q > best_q || (q == best_q && (total < best_sse || (total == best_sse && sizes[r] < sizes[best])))) { best = r; best_q = q; best_sse = total; }
+    }
+    return meets >= 0 ? meets : best >= 0 ? best : s->n_rungs - 1;
+}
 // The i-frame byte budget: the frame goes up into the session's staging, the probe sizes it at every rung, and the finest rung whose payload
 // fits becomes the current rung (the coarsest if none does; a rung the probe marks not encodable does not fit).  With a quality floor the
 // rate-distortion probe runs in its place and floor_rung chooses.
@@ -788,6 +846,14 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
     int rc = enc_staging(s);
     if (!rc && !staged) rc = upload_planes(e, y, u, v);
     uint32_t sizes[kMaxRungs];
+    if (e->sfloor_i > 0.0) {   // the SSIM probe in the RD probe's place
+        uint64_t sse[kMaxRungs][3];
+        int64_t q24[kMaxRungs][3];
+        if (!rc) rc = ssim_probe_staged(s, false, sizes, &sse[0][0], &q24[0][0]);
+        if (rc) return rc;
+        s->rung = ssim_floor_rung(e, sizes, &sse[0][0], &q24[0][0], e->budget_i, e->floor_i, e->sfloor_i);
+        return PFV_OK;
+    }
     if (e->floor_i > 0.0) {
         uint64_t sse[kMaxRungs][3];
         if (!rc) rc = rd_probe_staged(s, sizes, &sse[0][0]);
@@ -802,7 +868,7 @@ static int choose_iframe_rung(pfv_encoder *e, const uint8_t *y, const uint8_t *u
 }
 
 // an i-frame budget or floor applies: encode_iframe probes and chooses its rung
-static bool iframe_rung_rule(const pfv_encoder *e) { return (e->budget_i != 0 || e->floor_i > 0.0) && e->hot->n_rungs > 1; }   // one rung: nothing to choose
+static bool iframe_rung_rule(const pfv_encoder *e) { return (e->budget_i != 0 || e->floor_i > 0.0 || e->sfloor_i > 0.0) && e->hot->n_rungs > 1; }   // one rung: nothing to choose
 
 // Encoder::encode_iframe (src/enc.rs:75-123) behind pack_frame.  staged / probed: see choose_iframe_rung; settled: the frame lies in the staging
 // and the current rung is the one to write at (pfv_encoder_encode_frame under the p-frame floor)
@@ -858,14 +924,26 @@ PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const 
     if (!rc) rc = rd_probe_staged(e->hot, sizes_out, sse_out);
     return rc;
 }
+// ... and its SSIM sums per plane at every rung [n_rungs][3], from the same read of the frame
+PFV_API int pfv_encoder_probe_iframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!y || !u || !v || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_ssim: null buffer");
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    int rc = enc_staging(e->hot);
+    if (!rc) rc = upload_planes(e, y, u, v);
+    if (!rc) rc = ssim_probe_staged(e->hot, false, sizes_out, sse_out, ssim_q24_out);
+    return rc;
+}
 // the frame up into the session's staging and sized as a p-frame at every rung (counts: [n_rungs][kPProbeStats], or nullptr); sse
-// ([n_rungs][3], or nullptr): the rate-distortion probe in the size probe's place
-static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts, uint64_t *sse = nullptr)
+// ([n_rungs][3], or nullptr): the rate-distortion probe in the size probe's place; q24 ([n_rungs][3], or nullptr; with sse): the SSIM probe
+static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts, uint64_t *sse = nullptr,
+                               int64_t *q24 = nullptr)
 {
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
-    if (!rc) rc = sse ? prd_probe_staged(e->hot, sizes, sse, counts) : pprobe_staged(e->hot, sizes, counts);
+    if (!rc) rc = q24 ? ssim_probe_staged(e->hot, true, sizes, sse, q24, counts) : sse ? prd_probe_staged(e->hot, sizes, sse, counts) : pprobe_staged(e->hot, sizes, counts);
     return rc;
 }
 // payload bytes of this frame as a p-frame against the encoder's reference at every rung; the stream, the reference and the rung stay as they are
@@ -885,6 +963,15 @@ PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const 
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out);
+}
+// ... and its SSIM sums per plane at every rung [n_rungs][3]
+PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!y || !u || !v || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_ssim: null buffer");
+    if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
+    if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out, ssim_q24_out);
 }
 PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
 {
@@ -908,7 +995,14 @@ static bool hard_pframe_budget(const pfv_encoder *e) { return e->pprobe_on && e-
 static int write_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, bool staged = false)
 {
     int rc;
-    if (!staged && pframe_floor(e)) {
+    if (!staged && pframe_floor(e) && e->sfloor_p > 0.0) {   // the SSIM probe in the RD probe's place
+        uint32_t sizes[kMaxRungs];
+        uint64_t sse[kMaxRungs][3];
+        int64_t q24[kMaxRungs][3];
+        if ((rc = probe_pframe_planes(e, y, u, v, sizes, nullptr, &sse[0][0], &q24[0][0]))) return rc;
+        e->hot->rung = ssim_floor_rung(e, sizes, &sse[0][0], &q24[0][0], e->budget_p, e->floor_p, e->sfloor_p);
+        staged = true;
+    } else if (!staged && pframe_floor(e)) {
         uint32_t sizes[kMaxRungs];
         uint64_t sse[kMaxRungs][3];
         if ((rc = probe_pframe_planes(e, y, u, v, sizes, nullptr, &sse[0][0]))) return rc;
@@ -957,14 +1051,22 @@ static void write_dropframe(pfv_encoder *e)
 // and plane sums.  A candidate meets when its PSNR-YUV reaches the P-FRAME floor; exactly one meets: that one; both: fewer bytes, ties to the
 // i-frame; neither: the smaller squared error, then fewer bytes, then the i-frame.  A candidate that is not encodable (its sums are undefined)
 // never meets and loses to one that is; neither encodable: the i-frame, as today's rule.
-static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint64_t (&psse)[3], uint32_t ibytes, const uint64_t (&isse)[3])
+// pq / iq: the candidates' SSIM sums where the SSIM probe measured them (nullptr: the RD probe did; the p-frame SSIM floor is then off).  A
+// candidate meets when it meets every P-FRAME floor that is on; neither meets under the p-frame SSIM floor, in a frame that has windows: the
+// larger q24 total decides before the squared error.
+static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint64_t (&psse)[3], uint32_t ibytes, const uint64_t (&isse)[3],
+                              const int64_t *pq = nullptr, const int64_t *iq = nullptr)
 {
     if (ibytes == kEntErrOversize || pbytes == kEntErrOversize) return pbytes == kEntErrOversize;
-    const uint64_t samples = (uint64_t)pfv_frame_bytes(e->width, e->height);
     const uint64_t pt = psse[0] + psse[1] + psse[2], it = isse[0] + isse[1] + isse[2];
-    const bool pm = pfv_psnr(pt, samples) >= e->floor_p, im = pfv_psnr(it, samples) >= e->floor_p;
+    const double sfloor = pq && iq ? e->sfloor_p : 0.0;
+    const bool pm = meets_floors(e, psse, pq, e->floor_p, sfloor), im = meets_floors(e, isse, iq, e->floor_p, sfloor);
     if (pm != im) return im;
     if (pm) return ibytes <= pbytes;
+    if (sfloor > 0.0 && frame_windows(e) != 0) {
+        const int64_t pqt = pq[0] + pq[1] + pq[2], iqt = iq[0] + iq[1] + iq[2];
+        if (pqt != iqt) return iqt > pqt;
+    }
     return it != pt ? it < pt : ibytes <= pbytes;
 }
 // The frame's type chosen by the probes; the rules, in this order, are at the declaration (include/pfv_hip_ext.h)
@@ -982,16 +1084,21 @@ PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uin
     } else {
         uint32_t psize[kMaxRungs], isize[kMaxRungs], counts[kMaxRungs][kPProbeStats];
         uint64_t psse[kMaxRungs][3], isse[kMaxRungs][3];
+        int64_t pq[kMaxRungs][3], iq[kMaxRungs][3];
         const bool rd = pframe_floor(e);
-        if ((rc = probe_pframe_planes(e, y, u, v, psize, &counts[0][0], rd ? &psse[0][0] : nullptr))) return rc;   // 2: one upload, the p-frame sized (and measured) at every rung
-        const int rp = rd ? floor_rung(e, psize, &psse[0][0], e->budget_p, e->floor_p) : hard_pframe_budget(e) ? budget_rung(s, psize, e->budget_p) : s->rung;
+        const bool p_ssim = rd && e->sfloor_p > 0.0, i_ssim = rd && (p_ssim || (e->sfloor_i > 0.0 && s->n_rungs > 1));   // which probe measures each candidate
+        if ((rc = probe_pframe_planes(e, y, u, v, psize, &counts[0][0], rd ? &psse[0][0] : nullptr, p_ssim ? &pq[0][0] : nullptr))) return rc;   // 2: one upload, the p-frame sized (and measured) at every rung
+        const int rp = p_ssim ? ssim_floor_rung(e, psize, &psse[0][0], &pq[0][0], e->budget_p, e->floor_p, e->sfloor_p)
+                     : rd ? floor_rung(e, psize, &psse[0][0], e->budget_p, e->floor_p) : hard_pframe_budget(e) ? budget_rung(s, psize, e->budget_p) : s->rung;
         if (counts[rp][kPProbeCodedAt] == 0 && counts[rp][kPProbeMovedAt] == 0) {                   // 3: nothing to code, nothing moved: a drop frame
             type = 3;
             write_dropframe(e);
         } else if (rd) {                                                                            // 4 under the p-frame floor: the better of p at rp and i at ri
-            if ((rc = rd_probe_staged(s, isize, &isse[0][0]))) return rc;
-            const int ri = !iframe_rung_rule(e) ? s->rung : e->floor_i > 0.0 ? floor_rung(e, isize, &isse[0][0], e->budget_i, e->floor_i) : budget_rung(s, isize, e->budget_i);
-            if (rd_prefers_iframe(e, psize[rp], psse[rp], isize[ri], isse[ri])) {
+            if ((rc = i_ssim ? ssim_probe_staged(s, false, isize, &isse[0][0], &iq[0][0]) : rd_probe_staged(s, isize, &isse[0][0]))) return rc;
+            const int ri = !iframe_rung_rule(e) ? s->rung
+                         : e->sfloor_i > 0.0 ? ssim_floor_rung(e, isize, &isse[0][0], &iq[0][0], e->budget_i, e->floor_i, e->sfloor_i)
+                         : e->floor_i > 0.0 ? floor_rung(e, isize, &isse[0][0], e->budget_i, e->floor_i) : budget_rung(s, isize, e->budget_i);
+            if (rd_prefers_iframe(e, psize[rp], psse[rp], isize[ri], isse[ri], p_ssim ? pq[rp] : nullptr, p_ssim ? iq[ri] : nullptr)) {
                 s->rung = ri;
                 rc = write_iframe(e, y, u, v, true, nullptr, true);
             } else {                                                                                // 5: a p-frame at rp

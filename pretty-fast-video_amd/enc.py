@@ -17,11 +17,11 @@ from .frame import VideoFrame
 class Encoder:
     def __init__(self, writer, width: int, height: int, framerate: int, quality: int | None, ctx: Context, device_entropy: bool = True,
                  frame_report: bool = False, qualities=None, iframe_budget: int = 0, iframe_quality_floor: float = 0.0,
-                 pframe_quality_floor: float = 0.0, frame_ssim: bool = False):
+                 pframe_quality_floor: float = 0.0, frame_ssim: bool = False, iframe_ssim_floor: float = 0.0, pframe_ssim_floor: float = 0.0):
         """``qualities=[...]`` (next to ``quality=None``): a quality ladder -- 1..11 values in 0..10, strictly ascending (towards coarser
         quantisers); the header carries the tables of every rung and ``set_rung`` / ``set_rate`` choose per frame.  ``iframe_budget``: see
         ``set_iframe_budget``; ``iframe_quality_floor``: see ``set_iframe_quality_floor``; ``pframe_quality_floor``: see
-        ``set_pframe_quality_floor``"""
+        ``set_pframe_quality_floor``; ``iframe_ssim_floor`` / ``pframe_ssim_floor``: see ``set_iframe_ssim_floor`` / ``set_pframe_ssim_floor``"""
         self.ctx, self.writer = ctx, writer
         self.width, self.height = int(width), int(height)
         h = ctypes.c_void_p()
@@ -47,6 +47,10 @@ class Encoder:
             ctx.check(ctx._lib.pfv_encoder_set_iframe_quality_floor(h, float(iframe_quality_floor)))
         if pframe_quality_floor:
             ctx.check(ctx._lib.pfv_encoder_set_pframe_quality_floor(h, float(pframe_quality_floor)))
+        if iframe_ssim_floor:
+            ctx.check(ctx._lib.pfv_encoder_set_iframe_ssim_floor(h, float(iframe_ssim_floor)))
+        if pframe_ssim_floor:
+            ctx.check(ctx._lib.pfv_encoder_set_pframe_ssim_floor(h, float(pframe_ssim_floor)))
         self.finished = False
         ctx._sessions.add(self)
         self._flush()                                               # header (src/enc.rs:70)
@@ -157,6 +161,36 @@ class Encoder:
         -- if none does, the one with the smallest error; encode_frame then weighs that p-frame against the i-frame by the same measure
         (pfv_encoder_set_pframe_quality_floor)"""
         self.ctx.check(self.ctx._lib.pfv_encoder_set_pframe_quality_floor(self.handle, float(min_psnr_yuv)))
+
+    # SSIM probe and floors ------------------------------------------------------------------------------------------
+    def _probe_ssim(self, fn, frame: VideoFrame):
+        import numpy as np
+        sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
+        q24 = np.zeros((self.n_rungs, 3), dtype=np.int64)
+        self.ctx.check(fn(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels), ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse), ptr(q24)))
+        return sizes, sse, q24
+
+    def probe_iframe_ssim(self, frame: VideoFrame):
+        """(sizes uint32 [n_rungs], sse uint64 [n_rungs, 3], ssim_q24 int64 [n_rungs, 3]) of `frame` as an i-frame at every rung:
+        probe_iframe_rd's results and the SSIM sums per plane that last_ssim would show at that rung; nothing changes"""
+        self._check_frame(frame)
+        return self._probe_ssim(self.ctx._lib.pfv_encoder_probe_iframe_ssim, frame)
+
+    def probe_pframe_ssim(self, frame: VideoFrame):
+        """the same as a p-frame against the encoder's reference: probe_pframe_rd's results and the SSIM sums; nothing changes.
+        PfvError(PFV_ERR_STATE) when poisoned or finished"""
+        return self._probe_ssim(self.ctx._lib.pfv_encoder_probe_pframe_ssim, frame)
+
+    def set_iframe_ssim_floor(self, min_ssim: float = 0.0):
+        """floor on the frame's mean SSIM per i-frame (0: off; 1: the best-looking rung that fits): encode_iframe runs the SSIM probe and
+        takes, of the rungs within the i-frame budget that reach this floor and the PSNR floor, the one with the fewest bytes -- if none
+        does, the one with the largest SSIM; that rung becomes the current rung (pfv_encoder_set_iframe_ssim_floor)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_iframe_ssim_floor(self.handle, float(min_ssim)))
+
+    def set_pframe_ssim_floor(self, min_ssim: float = 0.0):
+        """the same per p-frame, within the set_rate budget (a hard cap here); encode_frame then weighs that p-frame against the i-frame
+        by the same measure (pfv_encoder_set_pframe_ssim_floor)"""
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_pframe_ssim_floor(self.handle, float(min_ssim)))
 
     def set_pframe_probe(self, on: bool = True):
         """on, with a set_rate budget and more than one rung: encode_pframe probes the frame and encodes it at the finest rung whose payload

@@ -138,6 +138,37 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_rd_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
                                                                  ctypes.c_void_p(sse_dev), ctypes.c_void_p(stats_dev or 0)))
 
+    # SSIM probe -----------------------------------------------------------
+    def _probe_ssim(self, fn, frames):
+        f = self._frames(frames)
+        sizes = np.zeros((self.n_streams, self.n_rungs), dtype=np.uint32)
+        sse = np.zeros((self.n_streams, self.n_rungs, 3), dtype=np.uint64)
+        q24 = np.zeros((self.n_streams, self.n_rungs, 3), dtype=np.int64)
+        self.ctx.check(fn(self.handle, ptr(f), ptr(sizes), ptr(sse), ptr(q24)))
+        return sizes, sse, q24
+
+    def probe_iframe_ssim(self, frames):
+        """(sizes uint32 [n_streams, n_rungs], sse uint64 [n_streams, n_rungs, 3], ssim_q24 int64 [n_streams, n_rungs, 3]) of every stream's
+        frame as an i-frame at every rung (pfv_enc_probe_iframe_ssim): probe_iframe_rd's results and the SSIM sums per plane (Y, U, V)
+        against the reconstruction that rung would leave in prev_frame.  Leaves prev_frame and the rung alone."""
+        return self._probe_ssim(self.ctx._lib.pfv_enc_probe_iframe_ssim, frames)
+
+    def probe_iframe_ssim_dev(self, frames_dev: int, sizes_dev: int, sse_dev: int, ssim_q24_dev: int, stats_dev: int = 0):
+        """asynchronous on the context's stream; as probe_iframe_rd_dev with ssim_q24_dev int64 [n_streams][n_rungs][3].  Honours the window
+        and the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_iframe_ssim_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
+                                                                   ctypes.c_void_p(sse_dev), ctypes.c_void_p(ssim_q24_dev), ctypes.c_void_p(stats_dev or 0)))
+
+    def probe_pframe_ssim(self, frames):
+        """the same as p-frames against the current prev_frame (pfv_enc_probe_pframe_ssim): probe_pframe_rd's results and the SSIM sums"""
+        return self._probe_ssim(self.ctx._lib.pfv_enc_probe_pframe_ssim, frames)
+
+    def probe_pframe_ssim_dev(self, frames_dev: int, sizes_dev: int, sse_dev: int, ssim_q24_dev: int, stats_dev: int = 0):
+        """asynchronous on the context's stream; as probe_pframe_rd_dev with ssim_q24_dev int64 [n_streams][n_rungs][3].  Honours the window
+        and the frame stride."""
+        self.ctx.check(self.ctx._lib.pfv_enc_probe_pframe_ssim_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(sizes_dev),
+                                                                   ctypes.c_void_p(sse_dev), ctypes.c_void_p(ssim_q24_dev), ctypes.c_void_p(stats_dev or 0)))
+
     # host-buffer forms ------------------------------------------------
     def _frames(self, frames) -> np.ndarray:
         f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)

@@ -54,6 +54,13 @@ launches (k_probe_pframe_rd + k_pprobe_rd_sizes); B = per rung pfv_enc_session_s
 size + pfv_enc_distortion_dev, the i-frame that restores prev_frame enqueued outside the rung's event pair; C = pfv_enc_probe_pframe_dev alone.
 Sizes and plane sums against the trial encodes at every rung of all streams; then the host clock around pfv_encoder: encode_pframe and
 encode_frame with the p-frame quality floor off / on.
+
+--probe-ssim / --probe-p-ssim: the SSIM probes (pfv_encoder_probe_iframe_ssim on the clip's first frame / pfv_encoder_probe_pframe_ssim on its
+second frame behind the first) -- probed against written payload bytes, reported squared error and reported SSIM sums per rung -- and then
+their timing at 96 x 1080p, ladders 0,2,5,7,10 and 0..10, by the methods above: A = the probe's three launches (k_probe_iframe_ssim or
+k_probe_pframe_ssim, k_probe_ssim_windows, the RD probe's tail); B = per rung the trial encode to the size + pfv_enc_distortion_dev +
+pfv_enc_ssim_dev; C = the RD probe of the same frame type (what the SSIM half adds is A - C).  Sizes, plane sums and SSIM sums against the
+trial encodes at every rung of all streams; the bytes of the block-sum map.
 """
 import argparse
 import ctypes
@@ -771,6 +778,127 @@ def time_pframe_floor_modes(pkg, ctx, ladder, w=1920, h=1080, n=14, rounds=3):
     return out
 
 
+def probe_ssim_line(pkg, ctx, w, h, kind, ladder, pframe):
+    """probed against written payload bytes, reported squared error and reported SSIM sums at every rung: the clip's first frame as an i-frame,
+    or its second frame as a p-frame behind the first at the middle rung"""
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    f0, f1 = (pkg.VideoFrame.from_packed(w, h, st.frame(t)) for t in (0, 1))
+    enc = pkg.Encoder(io.BytesIO(), w, h, 30, None, ctx, frame_report=True, frame_ssim=True, qualities=ladder)
+    probed, written, ssim = None, [], []
+    for r in range(len(ladder)):
+        if pframe:
+            enc.set_rung(len(ladder) // 2)
+            enc.encode_iframe(f0)
+        got = enc.probe_pframe_ssim(f1) if pframe else enc.probe_iframe_ssim(f0)
+        got = [[int(v) for v in np.asarray(x).reshape(-1)] for x in got]
+        assert probed is None or probed == got
+        probed = got
+        enc.set_rung(r)
+        enc.encode_pframe(f1) if pframe else enc.encode_iframe(f0)
+        rep, ss = enc.last_report, enc.last_ssim
+        written.append((rep.packet_bytes - 5, [int(v) for v in rep.sse], [int(v) for v in ss.q24]))
+        ssim.append(ss.ssim_all)
+    enc.close()
+    flat = [[x[0] for x in written], [v for x in written for v in x[1]], [v for x in written for v in x[2]]]
+    return {"ladder": ladder, "width": w, "height": h, "kind": kind, "pframe": pframe, "probed_bytes": probed[0], "probed_q24": probed[2],
+            "ssim_all": ssim, "equal": probed == flat}
+
+
+def time_probe_ssim(pkg, ctx, n_streams, ladder, pframe, w=1920, h=1080, warmup=3, samples=20, rounds=3):
+    """A = the SSIM probe's launch group; B = what it replaces on the same build, per rung a trial encode up to the size,
+    pfv_enc_distortion_dev and pfv_enc_ssim_dev; C = the RD probe.  Device events, warmed shapes; the answers compared rung by rung."""
+    lib = ctx._lib
+    fb, tb, R = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h)), len(ladder)
+    mid = R // 2
+    f0, f1 = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    sizes, sse, q24 = ctx.alloc(n_streams * R * 4), ctx.alloc(n_streams * R * 24), ctx.alloc(n_streams * R * 24)
+    sse_b, q_b = ctx.alloc(n_streams * 24), ctx.alloc(n_streams * 24)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    probe = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    upto = pkg.EncoderSession(ctx, w, h, None, n_streams, qualities=ladder)
+    full.enable_entropy()
+    upto.enable_entropy(payload_cap=24)            # the stage "up to the size", as time_probe
+    probe.set_rung(mid)
+    probe.encode_iframe_dev(f0, coef)              # p-frames: frame 0 as an i-frame at the middle rung is the state every measurement starts from
+    frame = f1 if pframe else f0
+    ev = [(ctx.event(), ctx.event()) for _ in range(R)]
+
+    def elapsed(pair):
+        ms = ctypes.c_float()
+        ctx.check(lib.pfv_event_elapsed_ms(pair[0], pair[1], ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sample(fn):
+        ctx.record(ev[0][0])
+        fn()
+        ctx.record(ev[0][1])
+        return elapsed(ev[0])
+
+    def trial_rung(s, r):
+        if pframe:
+            s.set_rung(mid)
+            s.encode_iframe_dev(f0, coef)          # outside the pair: prev_frame back to the state the probe sees
+        ctx.record(ev[r][0])
+        s.set_rung(r)
+        if pframe:
+            s.encode_pframe_dev(f1, mv, has, coef)
+            s.pack_pframe_dev(mv, has, coef)
+        else:
+            s.encode_iframe_dev(f0, coef)
+            s.pack_iframe_dev(coef)
+        s.distortion_dev(frame, sse_b)
+        s.ssim_dev(frame, q_b)
+        ctx.record(ev[r][1])
+
+    def sample_trials():
+        for r in range(R):
+            trial_rung(upto, r)
+        return sum(elapsed(p) for p in ev)
+
+    def median_ms(fn):
+        got = [fn() for _ in range(warmup + samples)]
+        return statistics.median(got[warmup:])
+    ssim_probe = (lambda: probe.probe_pframe_ssim_dev(f1, sizes, sse, q24)) if pframe else (lambda: probe.probe_iframe_ssim_dev(f0, sizes, sse, q24))
+    rd_probe = (lambda: probe.probe_pframe_rd_dev(f1, sizes, sse)) if pframe else (lambda: probe.probe_iframe_rd_dev(f0, sizes, sse))
+    res = {"ssim_probe": [], "trials": [], "rd_probe": []}
+    for _ in range(rounds):
+        res["ssim_probe"].append(median_ms(lambda: sample(ssim_probe)))
+        res["trials"].append(median_ms(sample_trials))
+        res["rd_probe"].append(median_ms(lambda: sample(rd_probe)))
+    ssim_probe()
+    got, got_sse, got_q = np.zeros((n_streams, R), np.uint32), np.zeros((n_streams, R, 3), np.uint64), np.zeros((n_streams, R, 3), np.int64)
+    ctx.download(got, sizes)
+    ctx.download(got_sse, sse)
+    ctx.download(got_q, q24)
+    same = {"sizes": [], "sse": [], "q24": []}
+    one, one_q = np.zeros((n_streams, 3), np.uint64), np.zeros((n_streams, 3), np.int64)
+    for r in range(R):
+        trial_rung(full, r)
+        same["sizes"].append(bool(np.array_equal(full.payload_sizes(), got[:, r])))
+        ctx.download(one, sse_b)
+        ctx.download(one_q, q_b)
+        same["sse"].append(bool(np.array_equal(one, got_sse[:, r])))
+        same["q24"].append(bool(np.array_equal(one_q, got_q[:, r])))
+    for a, b in ev:
+        ctx.event_destroy(a); ctx.event_destroy(b)
+    for s_ in (probe, full, upto):
+        s_.close()
+    for p in (f0, f1, coef, mv, has, sizes, sse, q24, sse_b, q_b):
+        ctx.free(p)
+    a, b, c = (statistics.median(res[k]) for k in ("ssim_probe", "trials", "rd_probe"))
+    spread = {k: max(v) - min(v) for k, v in res.items()}
+    windows = sum(pkg.ssim_windows(w, h)) if hasattr(pkg, "ssim_windows") else None
+    return {"shape": f"{n_streams} x {w}x{h}", "pframe": pframe, "ladder": ladder, "samples_per_round": samples, "rounds": rounds,
+            "A_ssim_probe_ms": a, "B_trials_ms": b, "C_rd_probe_ms": c, "spread_ms": spread, "A_over_B": a / b if b else None,
+            "A_below_B_by_more_than_Bs_spread": bool(a < b - spread["trials"]), "ssim_half_ms": a - c, "rounds_ms": res,
+            "map_bytes": n_streams * tb * (R * 128 + 64), "equal_per_rung": same, "bytes_stream0": [int(v) for v in got[0]],
+            "ssim_all_streams": [float(got_q[:, r].sum()) / (16777216.0 * windows * n_streams) for r in range(R)] if windows else None}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("width", type=int)
@@ -784,6 +912,8 @@ def main():
     ap.add_argument("--probe-p", action="store_true")
     ap.add_argument("--probe-rd", action="store_true")
     ap.add_argument("--probe-p-rd", action="store_true")
+    ap.add_argument("--probe-ssim", action="store_true")
+    ap.add_argument("--probe-p-ssim", action="store_true")
     ap.add_argument("--ssim", action="store_true")
     ap.add_argument("--time-ssim", action="store_true")
     ap.add_argument("--deblock", action="store_true")
@@ -837,6 +967,15 @@ def main():
             for lad in ([0, 2, 5, 7, 10], list(range(11))):
                 print(json.dumps({"pprobe_rd_timing": time_probe_p_rd(pkg, ctx, 96, lad)}), flush=True)
             print(json.dumps({"pprobe_rd_encoder_latency": time_pframe_floor_modes(pkg, ctx, [0, 2, 5, 7, 10])}), flush=True)
+        for on, pframe in ((a.probe_ssim, False), (a.probe_p_ssim, True)):
+            if not on:
+                continue
+            ladder = [int(x) for x in a.qualities.split(",") if x != ""]
+            print(json.dumps({"probe_ssim": probe_ssim_line(pkg, ctx, a.width, a.height, a.kind, ladder, pframe)}), flush=True)
+            if os.environ.get("PFV_HIP_LIB"):          # another build of the C ABI (the CPU emulator): nothing to time
+                continue
+            for lad in ([0, 2, 5, 7, 10], list(range(11))):
+                print(json.dumps({"probe_ssim_timing": time_probe_ssim(pkg, ctx, 96, lad, pframe)}), flush=True)
 
 
 if __name__ == "__main__":
