@@ -65,6 +65,8 @@ DEFAULT_RULES = {
     "quadrants": "tl_tr_bl_br",   # src/common.rs:145-149    ("tl_bl_tr_br")
     "pad_clear": "arg",           # src/common.rs:352-356 + src/enc.rs:84-90: pad colour 0 luma / 128 chroma ("zero")
     "u8_cast": "clamp",           # src/common.rs:321, :102  clamp(0, 255) before `as u8` ("wrap" = cast without the clamp)
+    "delta_clamp": "byte",        # src/common.rs:321 + :100-102  a p-frame's decoded term is a clamped byte d BEFORE prev + (d - 128) * 2:
+                                  #                        the term never exceeds 127 ("wide" = only the sum is clamped)
 }
 RULES = dict(DEFAULT_RULES)
 
@@ -220,11 +222,13 @@ def encode_blocks_delta(delta16: np.ndarray, q: np.ndarray) -> np.ndarray:
     return coef.reshape(-1, 256)
 
 
-def decode_blocks(coef: np.ndarray, q: np.ndarray) -> np.ndarray:
-    """src/common.rs:238-252 + :313-325; coef [n,256] i16 -> [n,16,16] u8."""
+def decode_blocks(coef: np.ndarray, q: np.ndarray, wide: bool = False) -> np.ndarray:
+    """src/common.rs:238-252 + :313-325; coef [n,256] i16 -> [n,16,16] u8 (wide: the i64 values before the clamp and the cast)."""
     n = coef.shape[0]
     m = dct_decode(coef.reshape(n, 4, 64), q).reshape(n, 4, 8, 8)
     px = _div_pow2(idct2d(m), 1 << FP_BITS, RULES["pixel_shift"]) + 128
+    if wide:
+        return _from_subblocks(px)
     if RULES["u8_cast"] != "clamp":
         return _from_subblocks((px & 255).astype(np.uint8))
     return _from_subblocks(np.clip(px, 0, 255).astype(np.uint8))
@@ -310,7 +314,7 @@ def decode_plane_delta(mv: np.ndarray, has: np.ndarray, coef: np.ndarray, bw: in
     """src/common.rs:448-475 + :254-285 + :98-104."""
     n = bw * bh
     out = np.zeros((n, 16, 16), dtype=np.uint8)
-    dec = decode_blocks(coef, q).astype(np.int64)
+    dec = decode_blocks(coef, q, wide=RULES["delta_clamp"] != "byte").astype(np.int64)
     for i in range(n):
         bx, by = (i % bw) * 16, (i // bw) * 16
         sx, sy = bx + int(mv[i, 0]), by + int(mv[i, 1])

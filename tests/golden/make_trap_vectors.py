@@ -2,7 +2,7 @@
 """Generates tests/golden/trap_vectors.npz: known-answer vectors aimed at the bit-exactness traps of SURVEY.md section 8c that
 tests/golden/hotpath_vectors.npz does not exercise (found by tests/test_mutation_sensitivity.py: flipping the rule left
 every older vector unchanged): pad colour on a ragged plane, exact ties in the motion search, the skip threshold met with
-equality, a best match on the last legal position of the plane, i32 wrap-around in decode.
+equality, a best match on the last legal position of the plane, i32 wrap-around in decode, the upper clamp of a p-frame's decoded term.
 
 Like the older vectors they are produced by the numpy oracle and cross-checked against the C oracle before being written
 (the Rust reference cannot run here and holds no expected values for this path).  python tests/golden/make_trap_vectors.py"""
@@ -70,6 +70,17 @@ r = np.random.default_rng(27)
 inp["host_coef"] = r.integers(-32768, 32768, (8, 256)).astype(np.int16)
 inp["host_q"] = r.integers(1, 65536, 64).astype(np.int32)
 
+# ---- the upper clamp of a p-frame's decoded term (src/common.rs:321 then :100-102: the term is a clamped BYTE d before prev + (d - 128) * 2, so
+# t = d - 128 never exceeds 127).  DC-only subblocks under the inter luma table of quality 5 (q[0] = 10): 101 .. 104 decode to t = 126, 127, 128, 130, their
+# negatives to -127 .. -130; over prev = 0 (t = 127 and the clamped 128 both give 254; unclamped, 128 would give 255), 1, 0 and 255
+cc = np.zeros((4, 256), np.int16)
+for mb, sign in enumerate((1, 1, -1, -1)):
+    cc[mb, 0::64] = [sign * 102, sign * 103, sign * 101, sign * 104]          # TL, TR, BL, BR
+inp["clamp_coef"] = cc
+inp["clamp_ref"] = np.repeat(np.array([0, 1, 0, 255], np.uint8), 16)[None, :].repeat(16, axis=0)
+terms = onp.decode_blocks(cc, onp.qtables(5)[2], wide=True)[:, ::8, ::8].reshape(4, 4) - 128
+assert terms[0].tolist() == [127, 128, 126, 130] and terms[2].tolist() == [-128, -129, -127, -130], terms.tolist()
+
 # outputs: numpy oracle; inputs that are themselves outputs of an earlier stage are filled in stage order
 t = dict(inp)
 _, ic, _, pc, px_err = onp.qtables(5)
@@ -94,6 +105,8 @@ for name in ("tie", "diag", "edge"):
     assert np.array_equal(omv, t[f"{name}_mv"]), name
     assert np.array_equal(ohas, t[f"{name}_has"]), name
     assert np.array_equal(oc, t[f"{name}_c1"]), name
+assert np.array_equal(t["clamp_rec"], ora.decode_plane_delta(np.zeros((4, 2), np.int8), np.ones(4, np.uint8), t["clamp_coef"], 4, 1, pl, t["clamp_ref"]))
+assert t["clamp_rec"][0, 0] == 254 and t["clamp_rec"][0, 8] == 254 and t["clamp_rec"][0, 16] == 255 and t["clamp_rec"][0, 24] == 255
 hq = t["host_q"]
 assert np.array_equal(t["host_rec"], np.stack([np.stack([ora.decode_subblock(t["host_coef"][i, k * 64:(k + 1) * 64], hq) for k in range(4)])
                                                for i in range(8)]).reshape(8, 2, 2, 8, 8).transpose(0, 1, 3, 2, 4).reshape(8, 16, 16))

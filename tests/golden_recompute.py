@@ -58,7 +58,7 @@ def recompute_hotpath(g):
 
 
 def recompute_traps(t):
-    """outputs of trap_vectors.npz from its inputs (rag_*, tie_*, diag_*, host_*)"""
+    """outputs of trap_vectors.npz from its inputs (rag_*, tie_*, diag_*, edge_*, host_*, clamp_*)"""
     out = {}
     _, ic, _, pc, px_err = onp.qtables(5)
     # ragged chroma-like plane: padding colour matters (src/common.rs:352-356, src/enc.rs:84-90)
@@ -80,6 +80,8 @@ def recompute_traps(t):
     out["edge_mv"], out["edge_has"], out["edge_c1"] = mv, has, c1
     # hostile coefficients and a q-table up to 65535: i32 wrap-around in decode (src/dct.rs:75-86, release arithmetic)
     out["host_rec"] = onp.decode_blocks(t["host_coef"], t["host_q"])
+    # a p-frame term of 127 and of 128 over prev = 0 and 1: the term is clamped as a byte before it is doubled (src/common.rs:321, :100-102)
+    out["clamp_rec"] = onp.decode_plane_delta(np.zeros((4, 2), np.int8), np.ones(4, np.uint8), t["clamp_coef"], 4, 1, pl, t["clamp_ref"])
     return out
 
 

@@ -441,7 +441,7 @@ def check_golden(pkg, ctx, oracle):
 def check_trap_vectors(pkg, ctx, oracle):
     """the HIP path against tests/golden/trap_vectors.npz: the vectors aimed at the bit-exactness traps of SURVEY.md section 8c
     (pad colour on a ragged plane, exact ties, skip threshold met with equality, last legal search position, i32 wrap in
-    decode); tests/test_mutation_sensitivity.py shows which rule each of them notices"""
+    decode, the upper clamp of a p-frame's term); tests/test_mutation_sensitivity.py shows which rule each of them notices"""
     import os
     t = np.load(os.path.join(os.path.dirname(__file__), "golden", "trap_vectors.npz"))
     _, ic, pl, pcq, px_err = oracle.qtables(5)
@@ -464,6 +464,93 @@ def check_trap_vectors(pkg, ctx, oracle):
     rec = pkg.VideoPlane.decode_plane(enc, t["host_q"], ctx).image()
     want = t["host_rec"].reshape(4, 2, 16, 16).transpose(0, 2, 1, 3).reshape(64, 32)
     assert np.array_equal(rec, want)
+    # the upper clamp of a p-frame's decoded term: t = 127 and 128 over prev = 0 and 1 (inverse_half's min(t, 127))
+    src = pkg.EncodedPPlane(64, 16, 4, 1, np.zeros((4, 2), np.int8), np.ones(4, np.uint8), t["clamp_coef"])
+    rec = pkg.VideoPlane.decode_plane_delta(src, pkg.VideoPlane.from_slice(64, 16, t["clamp_ref"]), pl, ctx).image()
+    assert np.array_equal(rec, t["clamp_rec"]), "the p-frame term's upper clamp (src/common.rs:321 before :100-102)"
+
+
+def check_bad_vector_edges(pkg, ctx, oracle):
+    """The first illegal vector and the last legal one (src/common.rs:258-259) on a 50 x 38 plane (padded: 64 x 48, 4 x 3 macroblocks): a
+    vector may point into the padding, not past it.  Legal vectors decode to the oracle's plane, illegal ones are PFV_ERR_BAD_MV for the
+    product and an error for the oracle; the kernel flags them and follows none (nothing is read outside the plane)."""
+    import pytest
+    bw, bh, pw, ph = 4, 3, 64, 48
+    q = oracle.qtables(5)[3]
+    rng = np.random.default_rng(50 * 38)
+    ref = rng.integers(0, 256, (ph, pw), dtype=np.uint8)
+    has = (np.arange(bw * bh) % 2).astype(np.uint8)
+    coef = np.zeros((bw * bh, 256), np.int16)
+    coef[has != 0, :6] = rng.integers(-20, 21, (int(has.sum()), 6))
+    mb = lambda col, row: row * bw + col
+    legal = [(mb(3, r), (0, 0)) for r in range(bh)] + [(mb(c, 2), (0, 0)) for c in range(bw)]      # last column, last row: into the padding
+    legal += [(mb(1, 1), v) for v in ((15, 15), (-15, -15), (15, -15), (-15, 15))]                  # interior
+    legal += [(mb(2, 1), (16, 16)), (mb(2, 0), (16, 0)), (mb(0, 1), (0, 16)), (mb(1, 1), (-16, -16))]   # the last legal position each way
+    illegal = [(mb(3, r), (1, 0)) for r in range(bh)] + [(mb(c, 2), (0, 1)) for c in range(bw)]
+    illegal += [(mb(0, r), (-1, 0)) for r in range(bh)] + [(mb(c, 0), (0, -1)) for c in range(bw)]
+    illegal += [(mb(2, 1), (17, 0)), (mb(2, 1), (0, 17)), (mb(1, 1), (-17, 0)), (mb(1, 1), (0, -17))]  # the first illegal one each way
+    refplane = pkg.VideoPlane.from_slice(pw, ph, ref)
+    for which, vec in legal + illegal:
+        mv = np.zeros((bw * bh, 2), np.int8)
+        mv[which] = vec
+        src = pkg.EncodedPPlane(pw, ph, bw, bh, mv, has, coef)
+        if (which, vec) in legal:
+            want = oracle.decode_plane_delta(mv, has, coef, bw, bh, q, ref)
+            got = pkg.VideoPlane.decode_plane_delta(src, refplane, q, ctx).image()
+            assert np.array_equal(got, want), f"legal vector {vec} on macroblock {which}: decoded plane differs from the oracle's"
+        else:
+            with pytest.raises(ValueError):
+                oracle.decode_plane_delta(mv, has, coef, bw, bh, q, ref)
+            with pytest.raises(pkg.PfvError) as e:
+                pkg.VideoPlane.decode_plane_delta(src, refplane, q, ctx)
+            assert e.value.code == pkg._lib.PFV_ERR_BAD_MV, (which, vec)
+    return len(legal), len(illegal)
+
+
+def check_session_bad_vector_stream(pkg, ctx, oracle, w=64, h=48, quality=5):
+    """A two-stream decoder session in which only stream 1 carries a bad vector: the p-frame call reports PFV_ERR_BAD_MV (pfv_dec_check, which
+    clears the flags), stream 0 has decoded its frame all the same and equals the oracle's; the next frames decode cleanly in BOTH streams."""
+    import pytest
+    from oracle_bind import OracleDecoder
+    tabs = np.stack(pkg.qtables_from_quality(quality)[:4])
+    streams = [pkg.SyntheticStream(w, h, seed=pkg.synth.SEED + 17 * s) for s in range(2)]
+    oencs = [oracle.encoder(w, h, quality) for _ in range(2)]
+    odecs = [OracleDecoder(oracle, w, h, tabs) for _ in range(2)]
+    dec = pkg.DecoderSession(ctx, w, h, tabs, 2)
+
+    def same(which, what):
+        fb = dec.framebuffer()
+        for s in which:
+            assert np.array_equal(fb[s], odecs[s].framebuffer()), f"{what}: stream {s}'s framebuffer differs from the oracle's"
+    try:
+        for t, kind in enumerate("IPIP"):
+            if kind == "I":
+                coef = np.stack([oencs[s].encode_iframe(streams[s].frame(t)) for s in range(2)])
+                dec.decode_iframe(coef)
+                for s in range(2):
+                    odecs[s].decode_iframe(coef[s])
+                same((0, 1), f"i-frame {t}")
+                continue
+            mv, has, coef = (np.stack(x) for x in zip(*[oencs[s].encode_pframe(streams[s].frame(t)) for s in range(2)]))
+            if t == 1:
+                bad = mv.copy()
+                bad[1, 0] = (-1, 0)                                  # stream 1, macroblock 0: one pixel left of the plane
+                with pytest.raises(pkg.PfvError) as e:
+                    dec.decode_pframe(bad, has, coef)
+                assert e.value.code == pkg._lib.PFV_ERR_BAD_MV
+                dec.check()                                          # reported once: the flags are cleared
+                odecs[0].decode_pframe(mv[0], has[0], coef[0])
+                with pytest.raises(ValueError):
+                    odecs[1].decode_pframe(bad[1], has[1], coef[1])
+                same((0,), "the p-frame whose stream 1 carries a bad vector")
+            else:
+                dec.decode_pframe(mv, has, coef)
+                dec.check()
+                for s in range(2):
+                    odecs[s].decode_pframe(mv[s], has[s], coef[s])
+                same((0, 1), f"p-frame {t}, behind the cleared vector")
+    finally:
+        dec.close()
 
 
 def check_colour_utils(pkg, ctx, oracle):

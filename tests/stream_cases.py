@@ -795,7 +795,9 @@ def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, patter
     in which ONE p-frame has the vector of macroblock 0 set to (-1, 0) -- outside the reference plane (src/common.rs:258-259); the kernels
     flag it and do not follow it.  For every place of the bad packet, batch shape, entropy path and pool size the GOP-batched decoder
     delivers on every call what the sequential Decoder delivers, the frames behind the error included; both agree with the oracle's decoder
-    up to the error; and the error is PFV_ERR_BAD_MV on the bad packet's call and on no other."""
+    up to the error; and the error is PFV_ERR_BAD_MV on the bad packet's call and on no other.
+    Then the FIRST illegal vector at the other borders, in the second GOP (another slot of the launch than the first: the flag is per slot):
+    (1, 0) on the last luma column, (0, 1) on the last luma row, (1, 0) on the last column of U -- two batch shapes x 2 entropy paths each."""
     tb = int(pkg._lib.load().pfv_total_blocks(w, h))
     tabs = pkg.qtables_from_quality(quality)
     tables = np.stack([np.asarray(tabs[k], np.int64).reshape(64) for k in range(4)])
@@ -806,8 +808,11 @@ def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, patter
         content.append((enc.encode_iframe(st.frame(t)), None, None) if c == "I" else enc.encode_pframe(st.frame(t))[::-1])   # (coef, has, mv)
     bad_mv = pkg._lib.PFV_ERR_BAD_MV
     runs = 0
-    for bad in bad_at:
+    bw, bh, cbw = (w + 15) // 16, (h + 15) // 16, (w // 2 + 15) // 16
+    borders = [(4, bw - 1, (1, 0)), (4, (bh - 1) * bw, (0, 1)), (4, bw * bh + cbw - 1, (1, 0))]
+    for bad, which, vector in [(k, 0, (-1, 0)) for k in bad_at] + borders:
         assert pattern[bad] == "P"
+        at_border = which != 0
         b = StreamBuilder(oracle, w, h, 30, tables, tb)
         for k, (coef, has, mv) in enumerate(content):
             if mv is None:
@@ -815,7 +820,7 @@ def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, patter
                 continue
             mv = mv.copy()
             if k == bad:
-                mv[0] = (-1, 0)
+                mv[which] = vector
             b.pframe(mv, has, coef, ENCODER_QIDX[2])
         data = b.bytes()
         want = _outcomes(lambda: pkg.Decoder(data, ctx, lookahead=0), pkg, n_calls=12, stop_at_error=False)
@@ -824,9 +829,9 @@ def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, patter
         assert want[bad] == ("err", bad_mv), (bad, want[bad])
         ora = _outcomes_oracle(oracle, data)
         assert ora == want[:bad + 1], (bad, [x[0] for x in ora], ora[-1][1:] if ora[-1][0] == "err" else None)
-        for max_gops, max_len in shapes:
+        for max_gops, max_len in (shapes[::2] if at_border else shapes):
             for mode in GOP_ENTROPY_MODES:
-                for threads in (0, 2):
+                for threads in ((2,) if at_border else (0, 2)):
                     got = _outcomes(lambda: pkg.GopDecoder(data, ctx, max_gops=max_gops, max_gop_frames=max_len, threads=threads, entropy=mode), pkg,
                                     n_calls=12, stop_at_error=False)
                     what = (bad, max_gops, max_len, mode, threads)
@@ -834,7 +839,8 @@ def check_gop_decoder_bad_vector(pkg, ctx, oracle, w=48, h=32, quality=5, patter
                     assert [k for k, x in enumerate(got) if x[0] == "err"] == [bad] and got[bad] == ("err", bad_mv), (what, got[bad])
                     assert got == want, (what, [x == y for x, y in zip(got, want)])
                     runs += 1
-    return runs
+    assert runs == len(bad_at) * len(shapes) * len(GOP_ENTROPY_MODES) * 2 + 3 * 2 * len(GOP_ENTROPY_MODES)
+    return runs - 3 * 2 * len(GOP_ENTROPY_MODES)      # the runs of the first part (the border vectors: 12 more)
 
 
 def check_gop_device_entropy(pkg, ctx, oracle, w, h, quality=5, pattern="IPPPPIPPPP", min_device_share=1.0, expect_unsettled=True, only=None):

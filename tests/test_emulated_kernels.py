@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import entd_cases as ec
 import parity_cases as pc
 import stream_cases as sc
 
@@ -98,6 +99,8 @@ def test_emu_bad_motion_vector(pkg, emu_ctx, oracle):
     with pytest.raises(pkg.PfvError) as e:
         pkg.VideoPlane.decode_plane_delta(src, ref, q, emu_ctx)
     assert e.value.code == pkg._lib.PFV_ERR_BAD_MV
+    assert pc.check_bad_vector_edges(pkg, emu_ctx, oracle) == (15, 18)
+    pc.check_session_bad_vector_stream(pkg, emu_ctx, oracle)
 
 
 def test_emu_stream_encoder_decoder(pkg, emu_ctx, oracle):
@@ -282,6 +285,34 @@ def test_emu_gop_decoder_device_entropy_small_stages():
     assert "3 passed" in r.stdout
 
 
+def test_emu_entd_regular_payloads(pkg, emu_ctx, oracle):
+    """k_entd_*: crafted payloads the device reader must keep (tests/entd_cases.py), default and 32-bit lanes, every decoder object"""
+    ec.check_regular(pkg, emu_ctx, oracle)
+
+
+def test_emu_entd_irregular_payloads(pkg, emu_ctx, oracle):
+    """k_entd_emit / k_hdr_emit: crafted payloads the device reader must leave to the host parser, frames and errors as the oracle's"""
+    ec.check_irregular(pkg, emu_ctx, oracle)
+
+
+def test_emu_entd_large_payloads(pkg, emu_ctx, oracle):
+    ec.check_large(pkg, emu_ctx, oracle)
+
+
+def test_emu_entd_small_stages():
+    """the crafted payloads through the variant build of test_emu_gop_decoder_device_entropy_small_stages: k_entd_emit stages 8 entries and 2
+    macroblock starts per workgroup, everything behind them takes the straight-to-memory branches"""
+    import subprocess
+    import sys
+    env = dict(os.environ, PFV_EMU_DEFS="-DPFV_ENT_WIN_WORDS=64 -DPFV_ED_OUT_CAP=8 -DPFV_ED_MB_CAP=2 -DPFV_HDR_SCAN_TILE=1", PFV_TEST_VARIANT_BUILD="1")
+    me = os.path.abspath(__file__)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
+                        me + "::test_emu_entd_regular_payloads", me + "::test_emu_entd_irregular_payloads", me + "::test_emu_entd_large_payloads"],
+                       env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "3 passed" in r.stdout
+
+
 def test_emu_gop_encoder_flush_and_errors(pkg, emu_ctx, oracle):
     sc.check_gop_encoder_flush_and_errors(pkg, emu_ctx, oracle)
 
@@ -297,7 +328,7 @@ def test_emu_gop_decoder_dense_iframe_failure(pkg, emu_ctx, oracle):
 
 
 def test_emu_gop_decoder_bad_vector(pkg, emu_ctx, oracle):
-    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes"""
+    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes, then 3 border vectors x 2 batch shapes x 2 entropy paths"""
     assert sc.check_gop_decoder_bad_vector(pkg, emu_ctx, oracle) == 36
 
 

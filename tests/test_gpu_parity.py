@@ -159,6 +159,8 @@ def test_bad_motion_vector_is_an_error(pkg, gpu_ctx, oracle):
         with pytest.raises(pkg.PfvError) as e:
             pkg.VideoPlane.decode_plane_delta(src, ref, q, gpu_ctx)
         assert e.value.code == pkg._lib.PFV_ERR_BAD_MV
+    assert pc.check_bad_vector_edges(pkg, gpu_ctx, oracle) == (15, 18)
+    pc.check_session_bad_vector_stream(pkg, gpu_ctx, oracle)
 
 
 def test_bad_arguments(pkg, gpu_ctx, oracle):
@@ -545,7 +547,7 @@ def test_gop_decoder_dense_iframe_failure(pkg, gpu_ctx, oracle):
 
 
 def test_gop_decoder_bad_vector(pkg, gpu_ctx, oracle):
-    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes"""
+    """PFV_ERR_BAD_MV on the call of the packet that carries the vector, and only there: 3 places x 3 batch shapes x 2 entropy paths x 2 pool sizes, then 3 border vectors x 2 batch shapes x 2 entropy paths"""
     assert sc.check_gop_decoder_bad_vector(pkg, gpu_ctx, oracle) == 36
 
 

@@ -30,6 +30,7 @@ VISIBLE = [
     ("resid_div", "floor", "src/common.rs:304 delta / 2 truncates", ("ext_out", "pf_c1")),
     ("quadrants", "tl_bl_tr_br", "src/common.rs:145-149 subblocks TL,TR,BL,BR", ("pf_c0", "pf_rec0")),
     ("pad_clear", "zero", "src/common.rs:352-356 + src/enc.rs:84-90 pad colour 128 for chroma", ("rag_c0",)),
+    ("delta_clamp", "wide", "src/common.rs:321 then :100-102 a p-frame's term is a clamped byte before it is doubled (t <= 127)", ("clamp_rec",)),
 ]
 
 # Unobservable by theorem -- asserted to change NOTHING, here and (for the forward transform) exhaustively in
