@@ -21,6 +21,11 @@ RATE_LADDER = [1, 3, 5, 8, 10]
 # (w, h, n_streams).  16x16: one macroblock per plane, chroma padded from 8 to 16; 18x34: padding in both directions, partial strips;
 # 130x18: luma 9 macroblocks wide (two strips, the second with one macroblock), chroma 65 -> 80; 50x38 x 3: stream indexing
 SHAPES = [(16, 16, 1), (18, 34, 1), (130, 18, 1), (50, 38, 3)]
+# shapes with strips that penc_search (csrc/pfv_kernels.hip) takes through its search levels WITHOUT bounds tests, for the probes' session checks;
+# the shapes above have none.  400x80: luma strips at x0 = 128 and 256, y0 = 16, 32, 48, no chroma ones (200x40); 544x96 x 2: luma ones, and in
+# each 272x48 chroma plane exactly one, at x0 = 128, y0 = 16, where the right and the bottom term of the rule hold with equality; two streams
+# over 32 tiles
+INTERIOR_SHAPES = [(400, 80, 1), (544, 96, 2)]
 
 
 def pad16(x):
@@ -129,11 +134,17 @@ def texture(rng, size=256):
     return t
 
 
+def texture_for(rng, rows, cols):
+    """texture() large enough to slice rows x cols from: the 256 one wherever it suffices (the generator's draws, and so every frame of such a
+    shape, stay what they were), else the next multiple of 256"""
+    return texture(rng, max(256, (max(rows, cols) + 255) // 256 * 256))
+
+
 def rate_clip(w, h, seed=7, n_frames=14):
     """luma: a twice box-smoothed noise texture panning 2 px per frame, frames 4-6 blended half and half with fresh noise, frames 9 and
     later static; chroma: a slow sinusoid"""
     rng = np.random.default_rng(seed)
-    tex = texture(rng)
+    tex = texture_for(rng, 8 + h, 18 + w)
     frames = []
     for t in range(n_frames):
         s = 2 * min(t, 9)
@@ -150,7 +161,8 @@ def rate_clip(w, h, seed=7, n_frames=14):
 def motion_clip(w, h, seed, n_frames):
     """a smoothed texture panning by (1, 2) px per frame with a little fresh noise: motion vectors, coded and skipped macroblocks"""
     rng = np.random.default_rng(seed)
-    tex = texture(rng)
+    tex = texture_for(rng, n_frames - 1 + max(20 * p + ph for p, (pw, ph) in enumerate(plane_dims(w, h))),
+                      2 * (n_frames - 1) + max(30 * p + pw for p, (pw, ph) in enumerate(plane_dims(w, h))))
     frames = []
     for t in range(n_frames):
         planes = []

@@ -26,6 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (w, h, n_streams).  16x16: one macroblock per plane, no room to move; 18x34: partial edge macroblocks; 130x18: two strips in a row;
 # 34x82: six macroblock rows = two stacked tiles, chroma 17x41; 50x38 x 3: stream indexing
 SHAPES = [(16, 16, 1), (18, 34, 1), (130, 18, 1), (34, 82, 1), (50, 38, 3)]
+INTERIOR_SHAPES = lc.INTERIOR_SHAPES                     # the p-frame probes search their strips without bounds tests: interior_mbs below
+INTERIOR_CASES = [(400, 80, 1, False), (400, 80, 1, True), (544, 96, 2, False)]                  # (w, h, n_streams, integer transform)
+INTERIOR_IDS = ["400x80x1-f32", "400x80x1-i32", "544x96x2-f32"]
 NSTATS = 20
 CODED, MOVED, HDR = 17, 18, 19
 CONTENT_KINDS = ["checker", "gradient", "noise", "texture"]
@@ -127,6 +130,59 @@ def check_inputs_cover(oracle, w, h, n):
     assert i_both
 
 
+def interior_mbs(pw, ph):
+    """the macroblocks (row-major indices in a padded plane of pw x ph) of the strips that penc_search searches without bounds tests.  Its rule,
+    restated: a strip is 8 macroblocks of one macroblock row from x0 = 128 sx, y0 = 16 by; it is interior when x0 >= 16, x0 + 8 * 16 + 16 <= pw,
+    y0 >= 16 and y0 + 32 <= ph"""
+    bw, bh = pw // 16, ph // 16
+    out = []
+    for by in range(bh):
+        for sx in range((bw + 7) // 8):
+            x0, y0 = 128 * sx, 16 * by
+            if x0 >= 16 and x0 + 8 * 16 + 16 <= pw and y0 >= 16 and y0 + 32 <= ph:
+                out += [by * bw + 8 * sx + m for m in range(8)]
+    return out
+
+
+def frame_interior_mbs(w, h):
+    """per plane: interior_mbs as indices into the frame's macroblock list (the planes' lists one behind the other)"""
+    out, off = [], 0
+    for pw, ph in lc.plane_dims(w, h):
+        pw, ph = lc.pad16(pw), lc.pad16(ph)
+        out.append(np.array(interior_mbs(pw, ph), np.int64) + off)
+        off += (pw // 16) * (ph // 16)
+    return out
+
+
+def check_interior_inputs(oracle, w, h, n, sets=None):
+    """of the MODEL alone, for a shape of INTERIOR_SHAPES: interior strips exist (in luma; at 544x96 in both chroma planes too), and over the
+    frame sets probed their macroblocks hold, at some rung, a vector with an odd component, one with a component of 4 or more, a zero vector, a
+    coded and a skipped macroblock -- in every plane that has interior strips, so that no plane's unchecked search is compared on zeros alone"""
+    per_plane = frame_interior_mbs(w, h)
+    assert [len(x) for x in per_plane] == {(400, 80): [48, 0, 0], (544, 96): [96, 8, 8]}[(w, h)]
+    # the smallest plane with an interior strip, and one step less either way
+    assert interior_mbs(272, 48) == list(range(17 + 8, 17 + 16)) and not interior_mbs(256, 48) and not interior_mbs(272, 32)
+    for p, idx in enumerate(per_plane):
+        if not len(idx):
+            continue
+        odd = big = zero = coded = skipped = 0
+        for state in (0, 1):
+            for got in facts(oracle, w, h, LADDER, n, state, sets):
+                if got is None:
+                    continue
+                for k in range(n):
+                    for r in range(len(LADDER)):
+                        has, mv = got[2][k][r][idx], got[3][k][r][idx].astype(np.int64)
+                        odd += int((mv & 1).any(axis=1).sum())
+                        big += int((np.abs(mv) >= 4).any(axis=1).sum())
+                        zero += int((mv == 0).all(axis=1).sum())
+                        coded += int(has.sum())
+                        skipped += int((~has).sum())
+        print(f"p-probe interior inputs {w}x{h}x{n} plane {p}: {len(idx)} interior macroblocks; over frames and rungs: odd vectors {odd}, |component| >= 4 {big}, "
+              f"zero vectors {zero}, coded {coded}, skipped {skipped}")
+        assert odd and big and zero and coded and skipped, (w, h, p)
+
+
 # ------------------------------------------------------------------ check 2: the session probe
 class PProbeRig(lc.SessionRig):
     """a SessionRig (encode buffers, entropy stage) with device buffers for the probe's frames (`stride` bytes apart), sizes and counts"""
@@ -168,6 +224,8 @@ def check_session_probe(pkg, ctx, oracle, w, h, n, int_transform=False, qualitie
     (or of the frame sets named by `sets`, which include 1) at every rung; once without the counts (stats_dev = NULL); the host-buffer form agrees"""
     if tuple(qualities) == tuple(LADDER):
         check_inputs_cover(oracle, w, h, n)
+        if (w, h, n) in INTERIOR_SHAPES:
+            check_interior_inputs(oracle, w, h, n, sets)
     with options(pkg, ctx, None, int_transform):
         rig = PProbeRig(pkg, ctx, w, h, qualities, n)
     try:
@@ -272,6 +330,55 @@ def check_window_stride(pkg, ctx, oracle, w=50, h=38, n=3):
         rig.enc.set_window(0, n)                                        # ... and the whole session again, still strided
         sizes, stats = rig.probe(fsets[4])
         assert np.array_equal(sizes, want[4][0]) and np.array_equal(stats, want[4][1])
+    finally:
+        rig.close()
+
+
+def unbounded_search(block, ref, bx, by):
+    """the reference's search (steps 8, 4, 2, 1 around the best so far; the centre first, then row by row, strict <) WITHOUT its bounds test, on
+    the plane as the kernels' window holds it: 16-column chunks and rows beyond the plane repeat the last ones inside -> (dx, dy)"""
+    ph, pw = ref.shape
+    rows = np.clip(np.arange(-16, ph + 16), 0, ph - 1)
+    cols = np.concatenate([np.arange(16), np.arange(pw), np.arange(pw - 16, pw)])
+    ext, block = ref[rows][:, cols].astype(np.int64), block.astype(np.int64)
+
+    def err(x, y):
+        return int(((ext[by + 16 + y:by + 32 + y, bx + 16 + x:bx + 32 + x] - block) ** 2).sum())
+    cx = cy = 0
+    best = err(0, 0)
+    for s in (8, 4, 2, 1):
+        e, _, x, y = min((err(cx + dx * s, cy + dy * s), 3 * dy + dx, cx + dx * s, cy + dy * s) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dx or dy)
+        if e < best:
+            best, cx, cy = e, x, y
+    return cx, cy
+
+
+def check_strip_on_the_right_border(pkg, ctx, oracle, w=256, h=48, rig_class=None):
+    """256x48: the luma strip at x0 = 128, y0 = 16 ends ON the right border (x0 + 8 * 16 == pw): it misses penc_search's rule by the 16 of its
+    right term alone and keeps its bounds tests.  No other shape of the suite has such a strip (pw a multiple of 128, >= 256).  Of the MODEL first:
+    under the pan the search without bounds tests answers otherwise for a macroblock of that strip, its match lying beyond the border.  Then the
+    probe's sizes and counts (`rig_class`: PProbeRig or one derived from it, for the other two p-frame probe kernels)"""
+    frames = [state_frames(w, h, 1, 0)[t] for t in (1, 2)]                                             # pan1, pan4
+    want = facts(oracle, w, h, LADDER, 1, 0, (1, 2))
+    ref = model_in_state(oracle, w, h, LADDER, 1, 0).prev[0][0]
+    # no interior strip as it is; 16 px wider, that one strip would be
+    assert 8 * 16 + 8 * 16 == ref.shape[1] == w and not interior_mbs(w, h) and interior_mbs(w + 16, h) == [(w + 16) // 16 + 8 + m for m in range(8)]
+    differs = 0
+    for f, t in zip(frames, (1, 2)):
+        src = lc.split(f[0], w, h)[0]
+        for i in range(w // 16 + 1, 2 * (w // 16)):              # the middle macroblock row; no vector of the last column can point right
+            bx, by = i % (w // 16) * 16, i // (w // 16) * 16
+            same = unbounded_search(src[by:by + 16, bx:bx + 16], ref, bx, by) == tuple(int(v) for v in want[t][3][0][0][i])
+            assert same or bx == w - 16, (t, i)                  # 16 px and more from every border the helper IS the model: no candidate leaves the plane
+            differs += int(not same)
+    print(f"p-probe {w}x{h}: frames whose last macroblock of the strip on the right border the search without bounds tests answers otherwise: {differs} of 2")
+    assert differs
+    rig = (rig_class or PProbeRig)(pkg, ctx, w, h, LADDER, 1)
+    try:
+        rig.to_state(0)
+        for f, t in zip(frames, (1, 2)):
+            sizes, stats = rig.probe(f)[:2]
+            assert np.array_equal(stats, want[t][1]) and np.array_equal(sizes, want[t][0]), FRAME_NAMES[t]
     finally:
         rig.close()
 

@@ -134,6 +134,8 @@ def check_session_probe(pkg, ctx, oracle, w, h, n, int_transform=False, qualitie
     of every frame set (or of those named by `sets`, which include 1) at every rung; once without the counts (stats_dev = NULL); the host-buffer
     form agrees; the rung stays"""
     check_inputs_cover(oracle)
+    if (w, h, n) in pp.INTERIOR_SHAPES and tuple(qualities) == tuple(LADDER):
+        pp.check_interior_inputs(oracle, w, h, n, sets)
     with options(pkg, ctx, None, int_transform):
         rig = PRdRig(pkg, ctx, w, h, qualities, n)
     try:

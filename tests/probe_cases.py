@@ -21,6 +21,10 @@ from ladder_cases import LADDER, SHAPES, DevBufs, LadderModel, frame_bytes, plan
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL_LADDER = list(range(11))
 KINDS = ["flat", "gradient", "texture", "noise", "checker"]
+# ladder_cases.INTERIOR_SHAPES for the i-frame probes: (w, h, n_streams, lane mapping, integer transform) -- both mappings and both transforms
+# at 400x80, the context's mapping and the float transform at 544x96 x 2
+INTERIOR_CASES = [(400, 80, 1, 1, False), (400, 80, 1, 1, True), (400, 80, 1, 2, False), (400, 80, 1, 2, True), (544, 96, 2, None, False)]
+INTERIOR_IDS = ["400x80x1-lanes8-f32", "400x80x1-lanes8-i32", "400x80x1-lanes16-f32", "400x80x1-lanes16-i32", "544x96x2-f32"]
 SENTINEL = 0xDEADBEEF
 NOT_ENCODABLE = 0xFFFFFFFF
 

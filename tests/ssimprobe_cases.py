@@ -221,6 +221,8 @@ def check_session_probe(pkg, ctx, oracle, w, h, n, int_transform=False, qualitie
     """real session calls make the states: i-frame at rung 1, probe, p-frame at rung 2, probe again.  Sizes, all 20 counts, the plane sums and the
     SSIM sums of every frame set (or of those named by `sets`, which include 1) at every rung; once without the counts (stats_dev = NULL); the
     host-buffer form agrees; the rung stays"""
+    if (w, h, n) in pp.INTERIOR_SHAPES and tuple(qualities) == tuple(LADDER):
+        pp.check_interior_inputs(oracle, w, h, n, sets)
     with options(pkg, ctx, None, int_transform):
         rig = PSsimRig(pkg, ctx, w, h, qualities, n)
     try:

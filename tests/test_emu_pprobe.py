@@ -12,6 +12,18 @@ def test_emu_pprobe_session(pkg, emu_ctx, oracle, w, h, n, int_transform):
     pp.check_session_probe(pkg, emu_ctx, oracle, w, h, n, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n", pp.INTERIOR_SHAPES)
+def test_emu_pprobe_interior_inputs(oracle, w, h, n):
+    """the oracle alone: no device, emulated or real"""
+    pp.check_inputs_cover(oracle, w, h, n)
+    pp.check_interior_inputs(oracle, w, h, n)
+
+
+@pytest.mark.parametrize("w,h,n,int_transform", pp.INTERIOR_CASES, ids=pp.INTERIOR_IDS)
+def test_emu_pprobe_session_interior(pkg, emu_ctx, oracle, w, h, n, int_transform):
+    pp.check_session_probe(pkg, emu_ctx, oracle, w, h, n, int_transform=int_transform)
+
+
 @pytest.mark.parametrize("int_transform", [False, True], ids=["f32", "i32"])
 def test_emu_pprobe_all_eleven_rungs(pkg, emu_ctx, oracle, int_transform):
     pp.check_session_probe(pkg, emu_ctx, oracle, 50, 38, 3, int_transform=int_transform, qualities=pp.FULL_LADDER)
@@ -28,6 +40,19 @@ def test_emu_pprobe_is_what_the_encoder_writes(pkg, emu_ctx, oracle, device_entr
 
 def test_emu_pprobe_window_and_stride(pkg, emu_ctx, oracle):
     pp.check_window_stride(pkg, emu_ctx, oracle)
+
+
+@pytest.mark.parametrize("device_entropy", [True, False], ids=["device_entropy", "host_entropy"])
+def test_emu_pprobe_is_what_the_encoder_writes_interior(pkg, emu_ctx, oracle, device_entropy):
+    pp.check_probe_is_what_the_encoder_writes(pkg, emu_ctx, oracle, device_entropy, 400, 80)
+
+
+def test_emu_pprobe_window_and_stride_interior(pkg, emu_ctx, oracle):
+    pp.check_window_stride(pkg, emu_ctx, oracle, 400, 80, 3)
+
+
+def test_emu_pprobe_strip_on_the_right_border(pkg, emu_ctx, oracle):
+    pp.check_strip_on_the_right_border(pkg, emu_ctx, oracle)
 
 
 def test_emu_pprobe_graph(pkg, emu_ctx, oracle):

@@ -16,6 +16,11 @@ def test_emu_prdprobe_session(pkg, emu_ctx, oracle, w, h, n, int_transform):
     prd.check_session_probe(pkg, emu_ctx, oracle, w, h, n, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,int_transform", prd.pp.INTERIOR_CASES, ids=prd.pp.INTERIOR_IDS)
+def test_emu_prdprobe_session_interior(pkg, emu_ctx, oracle, w, h, n, int_transform):
+    prd.check_session_probe(pkg, emu_ctx, oracle, w, h, n, int_transform=int_transform)
+
+
 def test_emu_prdprobe_all_eleven_rungs(pkg, emu_ctx, oracle):
     prd.check_session_probe(pkg, emu_ctx, oracle, 50, 38, 3, qualities=prd.FULL_LADDER, sets=[1, 2, 6])
 
@@ -35,6 +40,19 @@ def test_emu_prdprobe_no_side_effects(pkg, emu_ctx, oracle):
 
 def test_emu_prdprobe_window_and_stride(pkg, emu_ctx, oracle):
     prd.check_window_stride(pkg, emu_ctx, oracle)
+
+
+@pytest.mark.parametrize("device_entropy", [True, False], ids=["device_entropy", "host_entropy"])
+def test_emu_prdprobe_is_what_the_encoder_writes_interior(pkg, emu_ctx, oracle, device_entropy):
+    prd.check_probe_is_what_the_encoder_writes(pkg, emu_ctx, oracle, device_entropy, 400, 80)
+
+
+def test_emu_prdprobe_window_and_stride_interior(pkg, emu_ctx, oracle):
+    prd.check_window_stride(pkg, emu_ctx, oracle, 400, 80, 3)
+
+
+def test_emu_prdprobe_strip_on_the_right_border(pkg, emu_ctx, oracle):
+    prd.pp.check_strip_on_the_right_border(pkg, emu_ctx, oracle, rig_class=prd.PRdRig)
 
 
 def test_emu_prdprobe_graph(pkg, emu_ctx, oracle):

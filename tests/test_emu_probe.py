@@ -14,6 +14,11 @@ def test_emu_probe_session(pkg, emu_ctx, oracle, w, h, n, lanes, int_transform):
     pc.check_session_probe(pkg, emu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,lanes,int_transform", pc.INTERIOR_CASES, ids=pc.INTERIOR_IDS)
+def test_emu_probe_session_interior(pkg, emu_ctx, oracle, w, h, n, lanes, int_transform):
+    pc.check_session_probe(pkg, emu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
+
+
 @pytest.mark.parametrize("lanes", LANES, ids=["lanes8", "lanes16"])
 def test_emu_probe_all_eleven_rungs(pkg, emu_ctx, oracle, lanes):
     pc.check_session_probe(pkg, emu_ctx, oracle, 50, 38, 3, lane_mapping=lanes, qualities=pc.FULL_LADDER, sets=[0, 2])

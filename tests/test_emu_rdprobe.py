@@ -15,6 +15,11 @@ def test_emu_rdprobe_session(pkg, emu_ctx, oracle, w, h, n, lanes, int_transform
     rc.check_session_probe(pkg, emu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,lanes,int_transform", rc.pc.INTERIOR_CASES, ids=rc.pc.INTERIOR_IDS)
+def test_emu_rdprobe_session_interior(pkg, emu_ctx, oracle, w, h, n, lanes, int_transform):
+    rc.check_session_probe(pkg, emu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
+
+
 def test_emu_rdprobe_all_eleven_rungs(pkg, emu_ctx, oracle):
     rc.check_session_probe(pkg, emu_ctx, oracle, 50, 38, 3, qualities=rc.FULL_LADDER, sets=[0, 2])
 

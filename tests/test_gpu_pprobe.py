@@ -14,6 +14,11 @@ def test_gpu_pprobe_session(pkg, gpu_ctx, oracle, w, h, n, int_transform):
     pp.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,int_transform", pp.INTERIOR_CASES, ids=pp.INTERIOR_IDS)
+def test_gpu_pprobe_session_interior(pkg, gpu_ctx, oracle, w, h, n, int_transform):
+    pp.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
+
+
 @pytest.mark.parametrize("int_transform", [False, True], ids=["f32", "i32"])
 def test_gpu_pprobe_all_eleven_rungs(pkg, gpu_ctx, oracle, int_transform):
     pp.check_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, int_transform=int_transform, qualities=pp.FULL_LADDER)
@@ -30,6 +35,19 @@ def test_gpu_pprobe_is_what_the_encoder_writes(pkg, gpu_ctx, oracle, device_entr
 
 def test_gpu_pprobe_window_and_stride(pkg, gpu_ctx, oracle):
     pp.check_window_stride(pkg, gpu_ctx, oracle)
+
+
+@pytest.mark.parametrize("device_entropy", [True, False], ids=["device_entropy", "host_entropy"])
+def test_gpu_pprobe_is_what_the_encoder_writes_interior(pkg, gpu_ctx, oracle, device_entropy):
+    pp.check_probe_is_what_the_encoder_writes(pkg, gpu_ctx, oracle, device_entropy, 400, 80)
+
+
+def test_gpu_pprobe_window_and_stride_interior(pkg, gpu_ctx, oracle):
+    pp.check_window_stride(pkg, gpu_ctx, oracle, 400, 80, 3)
+
+
+def test_gpu_pprobe_strip_on_the_right_border(pkg, gpu_ctx, oracle):
+    pp.check_strip_on_the_right_border(pkg, gpu_ctx, oracle)
 
 
 def test_gpu_pprobe_graph(pkg, gpu_ctx, oracle):

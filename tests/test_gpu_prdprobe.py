@@ -14,6 +14,11 @@ def test_gpu_prdprobe_session(pkg, gpu_ctx, oracle, w, h, n, int_transform):
     prd.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,int_transform", prd.pp.INTERIOR_CASES, ids=prd.pp.INTERIOR_IDS)
+def test_gpu_prdprobe_session_interior(pkg, gpu_ctx, oracle, w, h, n, int_transform):
+    prd.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
+
+
 def test_gpu_prdprobe_all_eleven_rungs(pkg, gpu_ctx, oracle):
     prd.check_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, qualities=prd.FULL_LADDER, sets=[1, 2, 6])
 
@@ -33,6 +38,19 @@ def test_gpu_prdprobe_no_side_effects(pkg, gpu_ctx, oracle):
 
 def test_gpu_prdprobe_window_and_stride(pkg, gpu_ctx, oracle):
     prd.check_window_stride(pkg, gpu_ctx, oracle)
+
+
+@pytest.mark.parametrize("device_entropy", [True, False], ids=["device_entropy", "host_entropy"])
+def test_gpu_prdprobe_is_what_the_encoder_writes_interior(pkg, gpu_ctx, oracle, device_entropy):
+    prd.check_probe_is_what_the_encoder_writes(pkg, gpu_ctx, oracle, device_entropy, 400, 80)
+
+
+def test_gpu_prdprobe_window_and_stride_interior(pkg, gpu_ctx, oracle):
+    prd.check_window_stride(pkg, gpu_ctx, oracle, 400, 80, 3)
+
+
+def test_gpu_prdprobe_strip_on_the_right_border(pkg, gpu_ctx, oracle):
+    prd.pp.check_strip_on_the_right_border(pkg, gpu_ctx, oracle, rig_class=prd.PRdRig)
 
 
 def test_gpu_prdprobe_graph(pkg, gpu_ctx, oracle):

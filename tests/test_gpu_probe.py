@@ -16,6 +16,11 @@ def test_gpu_probe_session(pkg, gpu_ctx, oracle, w, h, n, lanes, int_transform):
     pc.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,lanes,int_transform", pc.INTERIOR_CASES, ids=pc.INTERIOR_IDS)
+def test_gpu_probe_session_interior(pkg, gpu_ctx, oracle, w, h, n, lanes, int_transform):
+    pc.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
+
+
 @pytest.mark.parametrize("lanes", LANES, ids=["lanes8", "lanes16"])
 def test_gpu_probe_all_eleven_rungs(pkg, gpu_ctx, oracle, lanes):
     pc.check_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, lane_mapping=lanes, qualities=pc.FULL_LADDER, sets=[0, 2])

@@ -17,6 +17,11 @@ def test_gpu_rdprobe_session(pkg, gpu_ctx, oracle, w, h, n, lanes, int_transform
     rc.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,lanes,int_transform", rc.pc.INTERIOR_CASES, ids=rc.pc.INTERIOR_IDS)
+def test_gpu_rdprobe_session_interior(pkg, gpu_ctx, oracle, w, h, n, lanes, int_transform):
+    rc.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
+
+
 def test_gpu_rdprobe_all_eleven_rungs(pkg, gpu_ctx, oracle):
     rc.check_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, qualities=rc.FULL_LADDER, sets=[0, 2])
 

@@ -23,6 +23,16 @@ def test_gpu_ssimprobe_session(pkg, gpu_ctx, oracle, w, h, n, int_transform):
     ssp.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
 
 
+@pytest.mark.parametrize("w,h,n,lanes,int_transform", ssp.pc.INTERIOR_CASES, ids=ssp.pc.INTERIOR_IDS)
+def test_gpu_ssimprobe_iframe_session_interior(pkg, gpu_ctx, oracle, w, h, n, lanes, int_transform):
+    ssp.check_iframe_session_probe(pkg, gpu_ctx, oracle, w, h, n, lane_mapping=lanes, int_transform=int_transform)
+
+
+@pytest.mark.parametrize("w,h,n,int_transform", ssp.pp.INTERIOR_CASES, ids=ssp.pp.INTERIOR_IDS)
+def test_gpu_ssimprobe_session_interior(pkg, gpu_ctx, oracle, w, h, n, int_transform):
+    ssp.check_session_probe(pkg, gpu_ctx, oracle, w, h, n, int_transform=int_transform)
+
+
 def test_gpu_ssimprobe_all_eleven_rungs(pkg, gpu_ctx, oracle):
     ssp.check_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, qualities=ssp.FULL_LADDER, sets=[1, 2, 6])
     ssp.check_iframe_session_probe(pkg, gpu_ctx, oracle, 50, 38, 3, qualities=ssp.FULL_LADDER, sets=[0, 2])
@@ -48,6 +58,19 @@ def test_gpu_ssimprobe_no_side_effects(pkg, gpu_ctx, oracle):
 
 def test_gpu_ssimprobe_window_and_stride(pkg, gpu_ctx, oracle):
     ssp.check_window_stride(pkg, gpu_ctx, oracle)
+
+
+@pytest.mark.parametrize("device_entropy", [True, False], ids=["device_entropy", "host_entropy"])
+def test_gpu_ssimprobe_is_what_the_encoder_writes_interior(pkg, gpu_ctx, oracle, device_entropy):
+    ssp.check_probe_is_what_the_encoder_writes(pkg, gpu_ctx, oracle, device_entropy, 400, 80)
+
+
+def test_gpu_ssimprobe_window_and_stride_interior(pkg, gpu_ctx, oracle):
+    ssp.check_window_stride(pkg, gpu_ctx, oracle, 400, 80, 3)
+
+
+def test_gpu_ssimprobe_strip_on_the_right_border(pkg, gpu_ctx, oracle):
+    ssp.pp.check_strip_on_the_right_border(pkg, gpu_ctx, oracle, rig_class=ssp.PSsimRig)
 
 
 def test_gpu_ssimprobe_graph(pkg, gpu_ctx, oracle):
