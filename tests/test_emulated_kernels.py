@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import ent_cases as nc
 import entd_cases as ec
 import parity_cases as pc
 import stream_cases as sc
@@ -308,6 +309,47 @@ def test_emu_entd_small_stages():
     me = os.path.abspath(__file__)
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
                         me + "::test_emu_entd_regular_payloads", me + "::test_emu_entd_irregular_payloads", me + "::test_emu_entd_large_payloads"],
+                       env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "3 passed" in r.stdout
+
+
+@pytest.mark.parametrize("name", sorted(nc.CASES))
+def test_emu_ent_cases(pkg, emu_ctx, oracle, name):
+    """k_ent_*: crafted coefficient / vector / flag buffers (tests/ent_cases.py) through the encoder session's pack calls: payloads == the
+    restatement's and the C oracle's, errors as the reference's panics.  Each case has proved on the restatement that it reaches its seam."""
+    case = nc.CASES[name]()
+    assert nc.check_device(pkg, emu_ctx, oracle, case) >= len(case.frames)
+
+
+def test_emu_ent_code_chunks(pkg, emu_ctx, oracle):
+    """k_ent_codes' second pass over a stream's groups (2048 x 1376: 258 of them); the 256-group twin runs on the GPU only"""
+    assert nc.check_device(pkg, emu_ctx, oracle, nc.LARGE["code_chunks_258_groups"]()) == 1
+
+
+@pytest.mark.parametrize("name", sorted(nc.WINDOW))
+def test_emu_ent_window_cases(pkg, emu_ctx, oracle, name):
+    """k_ent_pack's window (tests/ent_cases.py: window, Layout.window_events): steps that fill it to the last bit, one bit over, and single steps
+    larger than the window -- in the variant build of test_emu_ent_small_window, where the window holds 64 words; this build's 2 048 words take
+    the same inputs without leaving the window.  The production window cannot take the memory path at all: ent_cases.worst_step_bits() -- a
+    group's 16 384 coefficients pay for at most 1 075 fillers of 30 bits in front of 256 runs of 45 -- is 43 770 bits against 65 536."""
+    case = nc.WINDOW[name]()
+    if os.environ.get("PFV_TEST_VARIANT_BUILD") == "1":
+        assert "PFV_ENT_WIN_WORDS=64" in os.environ.get("PFV_EMU_DEFS", "")
+        mem, mem3 = nc.window_seams_of(case)
+        assert mem > 0 and (name != "long_symbols" or mem3 >= 8), "the 64-word window must send symbols (and third words) to memory"
+    assert nc.worst_step_bits() + 31 <= nc.WIN_BITS
+    assert nc.check_device(pkg, emu_ctx, oracle, case) >= len(case.frames)
+
+
+def test_emu_ent_small_window():
+    """the window cases, long_symbols and degenerate_tables in the variant build of test_emu_gop_decoder_device_entropy_small_stages: k_ent_pack's
+    window holds 64 words, so re-anchoring, the window's last bit and the memory path (ent_or_bits_mem, its third word included) all run"""
+    import subprocess
+    import sys
+    env = dict(os.environ, PFV_EMU_DEFS="-DPFV_ENT_WIN_WORDS=64 -DPFV_ED_OUT_CAP=8 -DPFV_ED_MB_CAP=2 -DPFV_HDR_SCAN_TILE=1", PFV_TEST_VARIANT_BUILD="1")
+    me = os.path.abspath(__file__)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider", me + "::test_emu_ent_window_cases"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "3 passed" in r.stdout
