@@ -131,6 +131,19 @@ inline std::vector<uint8_t> frames_deblock(Context &ctx, size_t width, size_t he
     return out;
 }
 
+// RGB / RGBA texture output (pfv_hip_ext.h, "RGB / RGBA texture output"): the pixel formats, and packed Y|U|V frames in host memory as tight
+// interleaved pictures, back to back (the reference's save_frame arithmetic)
+enum class PixelFormat { Rgb8 = PFV_PIX_RGB8, Rgba8 = PFV_PIX_RGBA8, Bgra8 = PFV_PIX_BGRA8 };
+inline size_t rgb_row_bytes(size_t width, PixelFormat format) { return pfv_rgb_row_bytes((int)width, (int)format); }
+inline std::vector<uint8_t> frames_to_rgb(Context &ctx, size_t width, size_t height, const std::vector<uint8_t> &frames, PixelFormat format)
+{
+    const size_t fb = pfv_frame_bytes((int)width, (int)height), row = rgb_row_bytes(width, format);
+    if (!fb || frames.empty() || frames.size() % fb) throw std::invalid_argument("frames_to_rgb: frames must hold whole packed frames");
+    std::vector<uint8_t> out(frames.size() / fb * row * height);
+    ctx.check(pfv_frames_to_rgb(ctx.handle(), (int)width, (int)height, (int)(frames.size() / fb), frames.data(), out.data(), (int)format));
+    return out;
+}
+
 // src/enc.rs:12-188
 class Encoder {
   public:
@@ -323,6 +336,7 @@ class Encoder {
 class Decoder {
   public:
     using OnVideo = std::function<void(const VideoFrame &)>;
+    using OnPicture = std::function<void(const std::vector<uint8_t> &pixels, uint32_t width, uint32_t height)>;   // one tight picture (set_output_rgb)
 
     Decoder(std::istream &reader, Context &ctx)
         : ctx_(ctx), data_((std::istreambuf_iterator<char>(reader)), std::istreambuf_iterator<char>())
@@ -344,14 +358,36 @@ class Decoder {
     // what the next p-frame predicts from is untouched
     void set_deblock(Deblock mode, const std::array<uint8_t, 3> &strength = {0, 0, 0}) { ctx_.check(pfv_decoder_set_deblock(h_, (int)mode, strength.data())); }
 
+    // every decoded frame as one tight picture in `format` instead of three planes: advance_frame_rgb / advance_delta_rgb then take the place of
+    // advance_frame / advance_delta (frames, order and errors are the same)
+    void set_output_rgb(bool on, PixelFormat format = PixelFormat::Rgb8)
+    {
+        ctx_.check(pfv_decoder_set_output_rgb(h_, on ? 1 : 0, (int)format));
+        rgb_bytes_ = on ? rgb_row_bytes(width(), format) * height() : 0;
+    }
+    bool advance_frame_rgb(const OnPicture &onpicture)
+    {
+        if (!rgb_bytes_) throw std::logic_error("Decoder::advance_frame_rgb: set_output_rgb(true) first");
+        pic_cb_ = &onpicture;
+        return result(pfv_decoder_advance_frame(h_, &Decoder::trampoline_rgb, this));
+    }
+    bool advance_delta_rgb(double delta, const OnPicture &onpicture)
+    {
+        if (!rgb_bytes_) throw std::logic_error("Decoder::advance_delta_rgb: set_output_rgb(true) first");
+        pic_cb_ = &onpicture;
+        return result(pfv_decoder_advance_delta(h_, delta, &Decoder::trampoline_rgb, this));
+    }
+
     // false at the end of the stream (Ok(false)), true otherwise; onvideo is called for every decoded frame
     bool advance_delta(double delta, const OnVideo &onvideo)                    // src/dec.rs:154-167
     {
+        if (rgb_bytes_) throw std::logic_error("Decoder::advance_delta: the callback gets RGB pictures (set_output_rgb): use advance_delta_rgb");
         cb_ = &onvideo;
         return result(pfv_decoder_advance_delta(h_, delta, &Decoder::trampoline, this));
     }
     bool advance_frame(const OnVideo &onvideo)                                  // src/dec.rs:169-224
     {
+        if (rgb_bytes_) throw std::logic_error("Decoder::advance_frame: the callback gets RGB pictures (set_output_rgb): use advance_frame_rgb");
         cb_ = &onvideo;
         return result(pfv_decoder_advance_frame(h_, &Decoder::trampoline, this));
     }
@@ -360,8 +396,15 @@ class Decoder {
     bool result(int rc)
     {
         cb_ = nullptr;
+        pic_cb_ = nullptr;
         if (rc < 0) ctx_.check(rc);
         return rc == 1;
+    }
+    static void trampoline_rgb(void *user, const uint8_t *y, const uint8_t *, const uint8_t *, int w, int h)
+    {
+        Decoder *d = static_cast<Decoder *>(user);
+        d->picture_.assign(y, y + d->rgb_bytes_);
+        if (d->pic_cb_ && *d->pic_cb_) (*d->pic_cb_)(d->picture_, (uint32_t)w, (uint32_t)h);
     }
     static void trampoline(void *user, const uint8_t *y, const uint8_t *u, const uint8_t *v, int w, int h)
     {
@@ -377,6 +420,9 @@ class Decoder {
     pfv_decoder *h_ = nullptr;
     VideoFrame frame_;              // retframe (src/dec.rs:22)
     const OnVideo *cb_ = nullptr;
+    std::vector<uint8_t> picture_;  // set_output_rgb: the picture the callback sees
+    size_t rgb_bytes_ = 0;          // its size; 0 while the switch is off
+    const OnPicture *pic_cb_ = nullptr;
 };
 
 // Encoder with the GOPs of the stream batched per launch (pfv_gop_encoder, pfv_hip.h): same calls, same .pfv bytes; a packet reaches the

@@ -403,6 +403,56 @@ PFV_API int pfv_dec_set_deblock(pfv_dec_session *s, int mode, const uint8_t stre
 /* pfv_decoder: forwards to its session; the callback then receives filtered frames, on the host and on the device output path */
 PFV_API int pfv_decoder_set_deblock(pfv_decoder *d, int mode, const uint8_t strength[3]);
 
+/* ------------------------------------------------------------------ RGB / RGBA texture output  [B]
+ * The last step of a decoder: the planar Y | U | V 4:2:0 frame as interleaved pixels a renderer can sample (the reference's README wishes for
+ * decoding "directly into a game-ready texture").  One launch, k_present_rgb (csrc/pfv_present_kernels.hip), converts n_streams frames; the
+ * source is PACKED or PADDED with its own stream stride (pfv_frames_sse_dev), so a session's padded framebuffer is read where it lies.
+ *   format          bytes / pixel   byte order
+ *   PFV_PIX_RGB8    3               R, G, B
+ *   PFV_PIX_RGBA8   4               R, G, B, 255
+ *   PFV_PIX_BGRA8   4               B, G, R, 255
+ * Arithmetic (normative): the reference's save_frame (src/lib.rs:361-394).  For the pixel (x, y), Y its luma sample and U, V the chroma
+ * samples at (x >> 1, y >> 1) (nearest doubling), in IEEE single precision, evaluated left to right, every product and sum rounded on its
+ * own (no fused multiply-add):
+ *     u = f32(U) - 128     v = f32(V) - 128     yy = f32(Y)
+ *     R = yy + 1.402 * v     G = yy - 0.344136 * u - 0.714136 * v     B = yy + 1.772 * u
+ * each converted as Rust's `as u8`: truncated toward zero, saturated to 0 .. 255.  These are the expressions of pfv_yuv420_to_rgb_dev.
+ * Width and height are positive, even and fit u16.
+ * Destination: rows `pitch` bytes apart (0 = pfv_rgb_row_bytes), pictures `stride` bytes apart (0 = pitch x height).  Exactly the
+ * width x bytes-per-pixel bytes of every row of every picture are written: nothing in the pitch padding, between or beyond the pictures.
+ * Aligned operands (source planes and rows to 4 bytes; destination base, pitch and stride to 4 bytes for RGB8, 16 for the others) take
+ * 4-byte loads and 12- / 16-byte non-temporal stores, anything else a byte-granular path with the same result.  No atomics, nothing
+ * allocated: a call is one kernel node of a recorded graph.  Measured on one MI355X: see profiles/present.md.
+ * PFV_ERR_BAD_ARG: a format or layout that does not exist, a null buffer, dimensions a frame cannot have, a pitch below the row size, a
+ * stride below pitch x height, a source stride below its layout's frame size, source and destination ranges that overlap. */
+enum { PFV_PIX_RGB8 = 0, PFV_PIX_RGBA8 = 1, PFV_PIX_BGRA8 = 2 };
+PFV_API size_t pfv_rgb_row_bytes(int width, int format);                       /* 0 for a bad format (or width <= 0) */
+/* asynchronous on the context's stream */
+PFV_API int pfv_frames_to_rgb_dev(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src_dev, int src_layout, size_t src_stride,
+                                  uint8_t *dst_dev, int format, size_t dst_pitch, size_t dst_stride);
+/* host buffers: PACKED in, tight pictures out; synchronises; PFV_ERR_STATE while a graph is being recorded */
+PFV_API int pfv_frames_to_rgb(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src, uint8_t *dst, int format);
+/* A decoder session's pictures: always the conversion of what pfv_dec_get_frame_dev would return at that moment -- with pfv_dec_set_deblock
+ * on, of the filtered picture (k_deblock into the planar output when a decode call has one, else into scratch of the session, then
+ * k_present_rgb from that packed frame; a fused kernel is not offered).  The scratch is allocated by whichever of pfv_dec_set_deblock /
+ * pfv_dec_set_output_rgb_dev / pfv_dec_get_frame_rgb* first needs it, never by a decode call (PFV_ERR_STATE if that moment lies inside a graph
+ * recording).
+ *   pfv_dec_get_frame_rgb_dev   all slots, pictures `stride` apart, asynchronous
+ *   pfv_dec_get_frame_rgb       all slots, tight, to host memory; synchronises; PFV_ERR_STATE while a graph is being recorded
+ *   pfv_dec_set_output_rgb_dev  an output IN ADDITION to the planar ones (pfv_dec_set_output_dev / _strided_dev and pfv_dec_get_frame* work
+ *                               unchanged beside it): while set, every pfv_dec_iframe* / pfv_dec_pframe* call (dense, sparse, lists) also
+ *                               writes the pictures of the slots of its window, indexed by slot, in one k_present_rgb from the new current
+ *                               framebuffer.  dst_dev NULL switches it off; the framebuffer and the planar outputs are bit for bit what they
+ *                               are without it.
+ * pfv_gop_decoder and pfv_batch_decoder have no switch of their own: pass their device frames to pfv_frames_to_rgb_dev. */
+PFV_API int pfv_dec_get_frame_rgb_dev(pfv_dec_session *s, uint8_t *dst_dev, int format, size_t pitch, size_t stride);
+PFV_API int pfv_dec_get_frame_rgb(pfv_dec_session *s, uint8_t *dst_host, int format);
+PFV_API int pfv_dec_set_output_rgb_dev(pfv_dec_session *s, uint8_t *dst_dev, int format, size_t pitch, size_t stride);
+/* pfv_decoder: while on, the callback's y points to ONE tight picture in `format` and u, v are NULL -- in host memory, or in device memory
+ * under pfv_decoder_set_output_device(1); lifetime as the planar frame's.  Results, order and errors of the advance calls are unchanged (a
+ * drop-frame packet calls back as little as it does without the switch). */
+PFV_API int pfv_decoder_set_output_rgb(pfv_decoder *d, int on, int format);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

@@ -37,6 +37,7 @@ PFV_ENTROPY_DECODE_AUTO, PFV_ENTROPY_DECODE_HOST, PFV_ENTROPY_DECODE_DEVICE = 0,
 PFV_ENC_TRANSFORM_AUTO, PFV_ENC_TRANSFORM_INT = 0, 1
 PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_frames_sse_dev
 PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_deblock / pfv_decoder_set_deblock
+PFV_PIX_RGB8, PFV_PIX_RGBA8, PFV_PIX_BGRA8 = 0, 1, 2             # pixel formats of pfv_frames_to_rgb* and the decoders' RGB outputs
 
 
 class PfvError(RuntimeError):
@@ -171,6 +172,13 @@ SIGNATURES = [
     ("pfv_frames_deblock", c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     ("pfv_dec_set_deblock", c_int, [_P, c_int, _P]),
     ("pfv_decoder_set_deblock", c_int, [_P, c_int, _P]),
+    ("pfv_rgb_row_bytes", c_size_t, [c_int, c_int]),
+    ("pfv_frames_to_rgb_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, _P, c_int, c_size_t, c_size_t]),
+    ("pfv_frames_to_rgb", c_int, [_P, c_int, c_int, c_int, _P, _P, c_int]),
+    ("pfv_dec_get_frame_rgb_dev", c_int, [_P, _P, c_int, c_size_t, c_size_t]),
+    ("pfv_dec_get_frame_rgb", c_int, [_P, _P, c_int]),
+    ("pfv_dec_set_output_rgb_dev", c_int, [_P, _P, c_int, c_size_t, c_size_t]),
+    ("pfv_decoder_set_output_rgb", c_int, [_P, c_int, c_int]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

@@ -207,6 +207,18 @@ static void dec_stop_workers(pfv_decoder *d)
     d->quit = false;
 }
 
+// where pfv_decoder_set_output_rgb's picture lands: pinned host memory, or device memory while the device output is on (either switch may come first)
+static int dec_rgb_buffers(pfv_decoder *d)
+{
+    pfv_ctx *ctx = d->ctx;
+    const size_t bytes = (size_t)d->width * d->height * 4;   // holds any format
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (d->rgb_on && !d->frame_dev && !d->rgbframe.resize(bytes)) return fail(ctx, PFV_ERR_NOMEM, "pfv_decoder_set_output_rgb: pinned staging");
+    if (d->rgb_on && d->frame_dev && !d->rgb_dev) HIP_TRY(ctx, hipMalloc((void **)&d->rgb_dev, bytes));
+    if (!(d->rgb_on && d->frame_dev) && d->rgb_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(d->rgb_dev); d->rgb_dev = nullptr; }
+    return PFV_OK;
+}
+
 extern "C" {
 
 // Packets parsed ahead of the one being decoded, on `n_threads` worker threads (0: parse inline, no threads).  The
@@ -232,6 +244,7 @@ PFV_API void pfv_decoder_destroy(pfv_decoder *d)
     (void)hipStreamSynchronize(d->ctx->stream);
     if (d->win_stream) { (void)hipStreamSynchronize(d->win_stream); (void)hipStreamDestroy(d->win_stream); }
     if (d->frame_dev) (void)hipFree(d->frame_dev);
+    if (d->rgb_dev) (void)hipFree(d->rgb_dev);
     for (DecWindow &w : d->win) w.destroy();
     pfv_dec_session_destroy(d->hot);
     delete d;
@@ -245,7 +258,17 @@ PFV_API int pfv_decoder_set_output_device(pfv_decoder *d, int on)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (on && !d->frame_dev) HIP_TRY(ctx, hipMalloc((void **)&d->frame_dev, pfv_frame_bytes(d->width, d->height)));
     if (!on && d->frame_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(d->frame_dev); d->frame_dev = nullptr; }
-    return PFV_OK;
+    return dec_rgb_buffers(d);
+}
+// on != 0: the callback's y points to ONE tight picture in `format` (PFV_PIX_*, pfv_rgb_row_bytes x height bytes) and u, v are NULL -- in host
+// memory, or in device memory under pfv_decoder_set_output_device(1); lifetime as the planar frame's.  Results, order and errors are unchanged.
+PFV_API int pfv_decoder_set_output_rgb(pfv_decoder *d, int on, int format)
+{
+    if (!d) return fail(nullptr, PFV_ERR_BAD_ARG, "null decoder");
+    if (on && !pfv_rgb_row_bytes(d->width, format)) return fail(d->ctx, PFV_ERR_BAD_ARG, "pfv_decoder_set_output_rgb: format must be PFV_PIX_RGB8, _RGBA8 or _BGRA8");
+    d->rgb_on = on != 0;
+    if (on) d->rgb_format = format;
+    return dec_rgb_buffers(d);
 }
 // out-of-loop deblocking of the frames the callback receives: the session's switch (both output paths fetch the frame from the session)
 PFV_API int pfv_decoder_set_deblock(pfv_decoder *d, int mode, const uint8_t strength[3])
@@ -410,7 +433,14 @@ PFV_API int pfv_decoder_advance_frame(pfv_decoder *d, pfv_video_cb onvideo, void
             rc = e->type == 1 ? pfv_dec_iframe_sparse(d->hot, e->idx.data(), e->val.data(), e->n_sparse, e->qidx)
                               : pfv_dec_pframe_sparse(d->hot, e->mv.data(), e->has.data(), e->idx.data(), e->val.data(),
                                                       e->n_sparse, e->qidx);
-        if (!rc && d->frame_dev) {   // pfv_decoder_set_output_device: the retframe stays in device memory
+        if (!rc && d->rgb_on) {      // pfv_decoder_set_output_rgb: one picture instead of the planes, on either side
+            if (d->frame_dev) {
+                rc = pfv_dec_get_frame_rgb_dev(d->hot, d->rgb_dev, d->rgb_format, 0, 0);
+                if (!rc) rc = pfv_ctx_sync(d->ctx);
+            } else {
+                rc = pfv_dec_get_frame_rgb(d->hot, d->rgbframe.data(), d->rgb_format);
+            }
+        } else if (!rc && d->frame_dev) {   // pfv_decoder_set_output_device: the retframe stays in device memory
             rc = pfv_dec_get_frame_dev(d->hot, d->frame_dev);
             if (!rc) rc = pfv_ctx_sync(d->ctx);
         } else if (!rc) {
@@ -424,7 +454,9 @@ PFV_API int pfv_decoder_advance_frame(pfv_decoder *d, pfv_video_cb onvideo, void
     dec_scan(d);       // refill the freed slot right away
     lk.unlock();
     if (rc) return rc;
-    if (kind == DecEvent::FRAME && onvideo) {
+    if (kind == DecEvent::FRAME && onvideo && d->rgb_on) {
+        onvideo(user, d->frame_dev ? d->rgb_dev : d->rgbframe.data(), nullptr, nullptr, d->width, d->height);
+    } else if (kind == DecEvent::FRAME && onvideo) {
         size_t ny = (size_t)d->width * d->height, nc = (size_t)(d->width / 2) * (d->height / 2);
         const uint8_t *f = d->frame_dev ? d->frame_dev : d->retframe.data();
         onvideo(user, f, f + ny, f + ny + nc, d->width, d->height);

@@ -171,10 +171,17 @@ struct pfv_dec_session {
     uint8_t db_fixed[3] = {0, 0, 0};         // PFV_DEBLOCK_FIXED: the strengths
     uint8_t db_auto[3] = {0, 0, 0};          // PFV_DEBLOCK_AUTO: pfv_deblock_strength of the tables the last decode call's qidx named
     std::vector<uint8_t> db_table;           // pfv_deblock_strength per q-table of the session
+    uint8_t *rgb_out = nullptr;              // RGB output beside the planar one (pfv_present.hip, pfv_dec_set_output_rgb_dev): pictures rgb_stride apart, by slot
+    int rgb_format = 0;                      // PFV_PIX_*
+    size_t rgb_pitch = 0, rgb_stride = 0;
+    uint8_t *db_scratch = nullptr;           // packed frames of all slots: where a deblocked picture waits for k_present_rgb when no planar output takes it
+    uint8_t *st_rgb = nullptr;               // staging of pfv_dec_get_frame_rgb
 };
 static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
 static int dec_deblock_win(pfv_dec_session *s, int first, int count, uint8_t *frames_out_dev, size_t out_stride);   // pfv_deblock.hip
 static int enc_ssim_enqueue(pfv_enc_session *s);     // pfv_ssim.hip
+static int dec_present_scratch(pfv_dec_session *s, const char *what);   // pfv_present.hip
+static int dec_present_step(pfv_dec_session *s);
 
 extern "C" {
 
@@ -705,7 +712,7 @@ PFV_API void pfv_dec_session_destroy(pfv_dec_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map, s->ssim_map};
+    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map, s->ssim_map, s->db_scratch, s->st_rgb};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -803,9 +810,10 @@ static int dec_step(pfv_dec_session *s, bool pframe, const int8_t *mv_dev, const
     if (rc) return rc;
     s->cur ^= 1;
     for (int i = 0; i < 3; i++) s->db_auto[i] = s->db_table[qidx[i]];   // dec_geom has checked the indices; a u8 names one of the first 256 tables
-    if (s->frames_out && s->db_mode) return dec_deblock_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
-    if (s->frames_out && !fused_output_ok(s)) return dec_crop_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
-    return PFV_OK;
+    if (s->frames_out && s->db_mode) rc = dec_deblock_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
+    else if (s->frames_out && !fused_output_ok(s)) rc = dec_crop_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
+    if (rc || !s->rgb_out) return rc;
+    return dec_present_step(s);   // the window's RGB pictures, from what has just been decoded (and filtered)
 }
 extern "C" {
 

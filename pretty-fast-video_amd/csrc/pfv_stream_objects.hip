@@ -498,6 +498,10 @@ struct pfv_decoder {
     double delta_accum = 0.0;
     PinnedBuf<uint8_t> retframe;           // Y|U|V, unpadded (src/dec.rs:22)
     uint8_t *frame_dev = nullptr;          // pfv_decoder_set_output_device: the retframe in device memory instead
+    bool rgb_on = false;                   // pfv_decoder_set_output_rgb: the callback gets one tight picture in rgb_format instead of the planes
+    int rgb_format = 0;
+    PinnedBuf<uint8_t> rgbframe;           // ... in host memory
+    uint8_t *rgb_dev = nullptr;            // ... in device memory (while frame_dev is set)
     // look-ahead: ring of events in stream order, [head, head + count)
     std::vector<std::unique_ptr<DecEvent>> ring;
     size_t head = 0, count = 0;

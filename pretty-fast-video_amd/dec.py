@@ -59,6 +59,14 @@ class Decoder:
         m, p, _keep = deblock_args(mode, strength)
         self.ctx.check(self.ctx._lib.pfv_decoder_set_deblock(self.handle, m, p))
 
+    def set_output_rgb(self, on=True, fmt="rgb8"):
+        """``onvideo`` receives one tight picture instead of a :class:`VideoFrame`: a uint8 array [height, width, 3 or 4] in fmt "rgb8" /
+        "rgba8" / "bgra8", or its DEVICE address (an int) under set_output_device (pfv_decoder_set_output_rgb)"""
+        from .quality import pix_format, rgb_shape
+        m = pix_format(fmt)
+        self.ctx.check(self.ctx._lib.pfv_decoder_set_output_rgb(self.handle, 1 if on else 0, m))
+        self._rgb_shape = rgb_shape(self.ctx, self.width(), self.height(), m) if on else None
+
     def entropy_counts(self) -> dict:
         """packets whose run streams the device read / that its stage left to the host parser (pfv_decoder_entropy_counts)"""
         a = (ctypes.c_long * 2)()
@@ -80,6 +88,12 @@ class Decoder:
     def _callback(self, onvideo):
         if getattr(self, "_device_out", False):
             return _CB(lambda _user, y, u, v, w, h: onvideo(int(y or 0)))
+        shape = getattr(self, "_rgb_shape", None)
+        if shape:
+            def cb_rgb(_user, y, u, v, w, h):
+                n = shape[0] * shape[1] * shape[2]
+                onvideo(np.ctypeslib.as_array(ctypes.cast(y, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy().reshape(shape))
+            return _CB(cb_rgb)
 
         def cb(_user, y, u, v, w, h):
             def arr(p, n):
@@ -178,6 +192,9 @@ class GopDecoder(Decoder):
 
     def reset(self):
         self.ctx.check(self.ctx._lib.pfv_gop_decoder_reset(self.handle))
+
+    def set_output_rgb(self, on=True, fmt="rgb8"):
+        raise NotImplementedError("pfv_gop_decoder has no RGB switch: pass its device frames to pfv_frames_to_rgb_dev")
 
     def _callback(self, onvideo):
         if not self.raw:

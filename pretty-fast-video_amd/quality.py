@@ -93,6 +93,35 @@ def frames_deblock(ctx: Context, width: int, height: int, frames, strength) -> n
     return out
 
 
+PIX_FORMATS = {"rgb8": _lib.PFV_PIX_RGB8, "rgba8": _lib.PFV_PIX_RGBA8, "bgra8": _lib.PFV_PIX_BGRA8}
+
+
+def pix_format(fmt) -> int:
+    """a pixel format of the RGB outputs: "rgb8" / "rgba8" / "bgra8" or a PFV_PIX_* value"""
+    return PIX_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+
+
+def rgb_shape(ctx: Context, width: int, height: int, fmt: int) -> tuple:
+    """(height, width, bytes per pixel) of one tight picture (pfv_rgb_row_bytes); raises for a format that does not exist"""
+    row = int(ctx._lib.pfv_rgb_row_bytes(int(width), int(fmt)))
+    if not row:
+        raise _lib.PfvError(_lib.PFV_ERR_BAD_ARG, "pixel format must be rgb8, rgba8 or bgra8")
+    return int(height), int(width), row // int(width)
+
+
+def frames_to_rgb(ctx: Context, width: int, height: int, frames, fmt="rgb8") -> np.ndarray:
+    """packed Y|U|V 4:2:0 frames (uint8, n frames) as interleaved pictures, uint8 [n, height, width, 3 or 4]: the reference's save_frame
+    arithmetic (include/pfv_hip_ext.h, "RGB / RGBA texture output"), fmt "rgb8" / "rgba8" / "bgra8" (pfv_frames_to_rgb)"""
+    fb = int(ctx._lib.pfv_frame_bytes(int(width), int(height)))
+    f = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    assert fb > 0 and f.size % fb == 0 and f.size
+    n = f.size // fb
+    m = pix_format(fmt)
+    out = np.empty((n,) + rgb_shape(ctx, width, height, m), dtype=np.uint8)
+    ctx.check(ctx._lib.pfv_frames_to_rgb(ctx.handle, int(width), int(height), n, ptr(f), ptr(out), m))
+    return out
+
+
 class FrameSsimStruct(ctypes.Structure):
     """pfv_frame_ssim"""
     _fields_ = [("q24", ctypes.c_int64 * 3), ("windows", ctypes.c_uint32 * 3), ("ssim", ctypes.c_double * 3), ("ssim_all", ctypes.c_double)]

@@ -436,6 +436,26 @@ class DecoderSession(_Geometry):
         m, p, _keep = deblock_args(mode, strength)
         self.ctx.check(self.ctx._lib.pfv_dec_set_deblock(self.handle, m, p))
 
+    # RGB / RGBA / BGRA pictures of what get_frame would return (k_present_rgb) ---------------
+    def get_frame_rgb(self, fmt="rgb8") -> np.ndarray:
+        """every stream's picture, tight: uint8 [n_streams, height, width, 3 or 4]; fmt "rgb8" / "rgba8" / "bgra8" (pfv_dec_get_frame_rgb)"""
+        from .quality import pix_format, rgb_shape
+        m = pix_format(fmt)
+        out = np.empty((self.n_streams,) + rgb_shape(self.ctx, self.width, self.height, m), dtype=np.uint8)
+        self.ctx.check(self.ctx._lib.pfv_dec_get_frame_rgb(self.handle, ptr(out), m))
+        return out
+
+    def get_frame_rgb_dev(self, dst_dev: int, fmt="rgb8", pitch: int = 0, stride: int = 0):
+        """asynchronous; rows `pitch` bytes apart (0: tight), pictures `stride` apart (0: pitch x height) (pfv_dec_get_frame_rgb_dev)"""
+        from .quality import pix_format
+        self.ctx.check(self.ctx._lib.pfv_dec_get_frame_rgb_dev(self.handle, ctypes.c_void_p(dst_dev), pix_format(fmt), int(pitch), int(stride)))
+
+    def set_output_rgb_dev(self, dst_dev, fmt="rgb8", pitch: int = 0, stride: int = 0):
+        """an RGB output beside the planar ones: every decode call also writes the pictures of its window's slots, indexed by slot
+        (None switches it off) (pfv_dec_set_output_rgb_dev)"""
+        from .quality import pix_format
+        self.ctx.check(self.ctx._lib.pfv_dec_set_output_rgb_dev(self.handle, ctypes.c_void_p(dst_dev or 0), pix_format(fmt), int(pitch), int(stride)))
+
     def framebuffer(self) -> np.ndarray:
         out = np.empty((self.n_streams, self.padded_frame_bytes), dtype=np.uint8)
         self.ctx.check(self.ctx._lib.pfv_dec_framebuffer(self.handle, ptr(out)))

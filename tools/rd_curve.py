@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -22,6 +22,13 @@ what was measured as raw packed frames: q<quality>_input.yuv, q<quality>_recon.y
 --time-deblock (on the GPU box) adds one more line: k_deblock against k_crop_frames on the same 96 x 1080p launch -- pfv_dec_get_frame_dev of
 one decoder session with the switch fixed at (5, 10, 10), at (0, 0, 0) (the copy path) and off -- HIP events around every launch, warm-up, the
 median of the samples, alternating in three rounds; and pfv_dec_pframe_dev with an output buffer set, switch off (fused crop) against auto.
+
+--time-present (on the GPU box) adds six lines, one per pixel format (RGB8, RGBA8, BGRA8) on 96 x 1080p and on one WIDTH x HEIGHT stream: the
+RGB pictures of a decoder session's frames (a) by pfv_dec_get_frame_rgb_dev -- one k_present_rgb from the padded framebuffer; (b) the way without
+it -- pfv_dec_get_frame_dev (k_crop_frames) plus one pfv_yuv420_to_rgb_dev per stream, which gives RGB8 only; (c) pfv_dec_get_frame_dev alone.
+HIP events around each, warm-up, the median of the samples, a / b / c alternating in three rounds; milliseconds, the bytes each must move
+(picture bytes read + bytes written) over its time, and (a)'s rate as a fraction of (c)'s.  With PFV_HIP_LIB set (another build of the C ABI:
+the CPU emulator) only the small shape runs, twice: the rows are printed, their times mean nothing.
 
 --time-kernel (on the GPU box) adds one more line: the k_sse_mb + k_sse_sum pair at the benched shape -- 96 streams of 1920 x 1080,
 input packed, reconstruction padded, map to scratch -- against pfv_dec_get_frame_dev (k_crop_frames) over the same 96 frames, which
@@ -282,6 +289,56 @@ def time_deblock(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
             "bytes_per_launch": bytes_moved, "deblock_GBps": bytes_moved / med["deblock"] / 1e6, "crop_GBps": bytes_moved / med["crop"] / 1e6,
             "dec_pframe_plus_output_off_ms": statistics.median(m for m, _, _ in loop["off"]),
             "dec_pframe_plus_output_auto_ms": statistics.median(m for m, _, _ in loop["auto"]), "dec_pframe_rounds_ms": loop}
+
+
+def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
+    lib = ctx._lib
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    bpp = int(lib.pfv_rgb_row_bytes(w, pkg.quality.pix_format(fmt))) // w
+    f0, planar, coef = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams), ctx.alloc(n_streams * tb * 512)
+    rgb, rgb3 = ctx.alloc(w * h * bpp * n_streams), ctx.alloc(w * h * 3 * n_streams)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, f0)
+    enc = pkg.EncoderSession(ctx, w, h, 5, n_streams)
+    dec = pkg.DecoderSession(ctx, w, h, np.stack(pkg.qtables_from_quality(5)[:4]), n_streams)
+    enc.encode_iframe_dev(f0, coef)
+    dec.decode_iframe_dev(coef)                   # the framebuffer holds decoded pictures
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got), min(got), max(got)
+
+    def without():                                # the crop, then one launch per stream: RGB8 whatever `fmt` is
+        dec.get_frame_dev(planar)
+        for k in range(n_streams):
+            ctx.check(lib.pfv_yuv420_to_rgb_dev(ctx.handle, ctypes.c_void_p(planar + k * fb), w, h, ctypes.c_void_p(rgb3 + k * w * h * 3)))
+    ways = {"a_present": lambda: dec.get_frame_rgb_dev(rgb, fmt), "b_crop_plus_per_stream": without, "c_crop": lambda: dec.get_frame_dev(planar)}
+    res = {k: [] for k in ways}
+    for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
+        for key, fn in ways.items():
+            res[key].append(median_ms(fn))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    enc.close(); dec.close()
+    for p in (f0, planar, coef, rgb, rgb3):
+        ctx.free(p)
+    med = {k: statistics.median(m for m, _, _ in v) for k, v in res.items()}
+    moved = {"a_present": n_streams * (fb + w * h * bpp), "b_crop_plus_per_stream": n_streams * (2 * fb + fb + w * h * 3), "c_crop": n_streams * 2 * fb}
+    over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
+    gbps = {k: over(moved[k], med[k] * 1e6) for k in ways}
+    return {"shape": f"{n_streams} x {w}x{h}", "format": fmt, "samples_per_round": samples, "rounds": rounds,
+            "a_present_ms": med["a_present"], "b_crop_plus_per_stream_ms": med["b_crop_plus_per_stream"], "c_crop_ms": med["c_crop"],
+            "bytes": moved, "GBps": gbps, "a_over_b_time": over(med["a_present"], med["b_crop_plus_per_stream"]),
+            "a_rate_over_c_rate": over(gbps["a_present"], gbps["c_crop"]) if gbps["a_present"] else None, "rounds_ms": res}
 
 
 def time_kernels(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
@@ -919,6 +976,7 @@ def main():
     ap.add_argument("--deblock", action="store_true")
     ap.add_argument("--dump", default=None)
     ap.add_argument("--time-deblock", action="store_true")
+    ap.add_argument("--time-present", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -932,6 +990,12 @@ def main():
             print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
         if a.time_deblock:
             print(json.dumps({"time_deblock": time_deblock(pkg, ctx)}), flush=True)
+        if a.time_present:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the rows only
+            for shape in ([] if emu else [dict(n_streams=96, w=1920, h=1080)]) + [dict(n_streams=1, w=a.width, h=a.height)]:
+                for fmt in ("rgb8", "rgba8", "bgra8"):
+                    kw = dict(warmup=1, samples=2, rounds=1) if emu else {}
+                    print(json.dumps({"time_present": time_present(pkg, ctx, fmt, **shape, **kw)}), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
         if a.probe:
