@@ -144,6 +144,19 @@ inline std::vector<uint8_t> frames_to_rgb(Context &ctx, size_t width, size_t hei
     return out;
 }
 
+// RGB / RGBA picture input (pfv_hip_ext.h, "RGB / RGBA picture input"): the chroma modes, and tight interleaved pictures in host memory, back
+// to back, as packed Y|U|V frames (the reference's load_frame arithmetic; Box: the mean of the 2 x 2 pixels' chroma instead of the even pixel's)
+enum class ChromaMode { Point = PFV_CHROMA_POINT, Box = PFV_CHROMA_BOX };
+inline std::vector<uint8_t> frames_from_rgb(Context &ctx, size_t width, size_t height, const std::vector<uint8_t> &pictures, PixelFormat format,
+                                            ChromaMode chroma = ChromaMode::Point)
+{
+    const size_t fb = pfv_frame_bytes((int)width, (int)height), pic = rgb_row_bytes(width, format) * height;
+    if (!fb || !pic || pictures.empty() || pictures.size() % pic) throw std::invalid_argument("frames_from_rgb: pictures must hold whole tight pictures");
+    std::vector<uint8_t> out(pictures.size() / pic * fb);
+    ctx.check(pfv_frames_from_rgb(ctx.handle(), (int)width, (int)height, (int)(pictures.size() / pic), pictures.data(), out.data(), (int)format, (int)chroma));
+    return out;
+}
+
 // src/enc.rs:12-188
 class Encoder {
   public:
@@ -194,6 +207,33 @@ class Encoder {
         ctx_.check(pfv_encoder_finish(h_));
         finished_ = true;
         flush();
+    }
+    // every frame as one tight picture in `format` instead of three planes: encode_iframe_rgb / encode_pframe_rgb / encode_frame_rgb then take
+    // the place of the VideoFrame methods, which throw while the switch is on (the C ABI's probe calls take the picture as y with u = v = NULL)
+    void set_input_rgb(bool on, PixelFormat format = PixelFormat::Rgb8, ChromaMode chroma = ChromaMode::Point)
+    {
+        ctx_.check(pfv_encoder_set_input_rgb(h_, on ? 1 : 0, (int)format, (int)chroma));
+        rgb_bytes_ = on ? rgb_row_bytes(width_, format) * height_ : 0;
+    }
+    void encode_iframe_rgb(const std::vector<uint8_t> &picture)
+    {
+        check_picture(picture);
+        ctx_.check(pfv_encoder_encode_iframe(h_, picture.data(), nullptr, nullptr));
+        flush();
+    }
+    void encode_pframe_rgb(const std::vector<uint8_t> &picture)
+    {
+        check_picture(picture);
+        ctx_.check(pfv_encoder_encode_pframe(h_, picture.data(), nullptr, nullptr));
+        flush();
+    }
+    int encode_frame_rgb(const std::vector<uint8_t> &picture)   // -> 1 i-frame, 2 p-frame, 3 drop frame (pfv_encoder_encode_frame)
+    {
+        check_picture(picture);
+        int type = 0;
+        ctx_.check(pfv_encoder_encode_frame(h_, picture.data(), nullptr, nullptr, &type));
+        flush();
+        return type;
     }
     // packet payloads from the device entropy stage (default) or the host serialisers: same bytes
     void set_device_entropy(bool on) { ctx_.check(pfv_encoder_set_device_entropy(h_, on ? 1 : 0)); }
@@ -311,8 +351,14 @@ class Encoder {
     }
 
   private:
+    void check_picture(const std::vector<uint8_t> &picture) const
+    {
+        if (!rgb_bytes_) throw std::logic_error("Encoder: set_input_rgb(true) first");
+        if (picture.size() != rgb_bytes_) throw std::invalid_argument("Encoder: the picture is not one tight picture of the encoder's size and format");
+    }
     void check_frame(const VideoFrame &f) const   // the asserts of src/enc.rs:76-80
     {
+        if (rgb_bytes_) throw std::logic_error("Encoder: the encoder takes RGB pictures (set_input_rgb): use the _rgb methods");
         if (f.width != width_ || f.height != height_ || f.plane_y.pixels.size() != width_ * height_ ||
             f.plane_u.pixels.size() != (width_ / 2) * (height_ / 2) || f.plane_v.pixels.size() != (width_ / 2) * (height_ / 2))
             throw std::invalid_argument("Encoder: frame geometry does not match the encoder (src/enc.rs:76-79)");
@@ -328,6 +374,7 @@ class Encoder {
     Context &ctx_;
     std::ostream &out_;
     size_t width_, height_;
+    size_t rgb_bytes_ = 0;          // set_input_rgb: the size of one picture; 0 while the switch is off
     bool finished_ = false;
     pfv_encoder *h_ = nullptr;
 };

@@ -453,6 +453,57 @@ PFV_API int pfv_dec_set_output_rgb_dev(pfv_dec_session *s, uint8_t *dst_dev, int
  * drop-frame packet calls back as little as it does without the switch). */
 PFV_API int pfv_decoder_set_output_rgb(pfv_decoder *d, int on, int format);
 
+/* ------------------------------------------------------------------ RGB / RGBA picture input  [B]
+ * The first step of an encoder, the mirror of the texture output: interleaved pixels as a renderer, a capture API or an image decoder hands
+ * them over become the planar Y | U | V 4:2:0 frame every encoder entry point takes.  One launch, k_ingest_rgb
+ * (csrc/pfv_ingest_kernels.hip), converts n_streams pictures.  Formats and byte orders: PFV_PIX_* above; the alpha byte of the 4-byte formats
+ * is read and ignored, any value is accepted.
+ * Source: rows `pitch` bytes apart (0 = pfv_rgb_row_bytes), pictures `stride` bytes apart (0 = pitch x height).
+ * Destination: PACKED frames (Y | U | V as pfv_frame_bytes lays them out) `dst_stride` bytes apart (0 = pfv_frame_bytes).  Exactly the
+ * frames' bytes are written: nothing between or beyond them.
+ * Arithmetic (normative): the reference's load_frame (src/lib.rs:340-346).  For a pixel's bytes R, G, B as f32, in IEEE single precision,
+ * evaluated left to right, every product and sum rounded on its own (no fused multiply-add):
+ *     Y = ((0.299 * R) + (0.587 * G)) + (0.114 * B)
+ *     U = ((128 - (0.168736 * R)) - (0.331264 * G)) + (0.5 * B)
+ *     V = ((128 + (0.5 * R)) - (0.418688 * G)) - (0.081312 * B)
+ * each converted as Rust's `as u8`: truncated toward zero, saturated to 0 .. 255.  These are the expressions of pfv_rgb_to_yuv420_dev.
+ * The luma sample (x, y) is the pixel's Y.  The chroma sample (cx, cy) depends on the chroma mode:
+ *   PFV_CHROMA_POINT  the U, V of pixel (2cx, 2cy): VideoFrame::from_planes -> reduce() (src/frame.rs:51-59), bit-identical to
+ *                     pfv_rgb_to_yuv420_dev.  Three quarters of the chroma information are dropped, which aliases on fine colour detail.
+ *   PFV_CHROMA_BOX    with a, b, c, d the u8 U (or V) values above of the four pixels (2cx + {0, 1}, 2cy + {0, 1}): (a + b + c + d + 2) >> 2
+ *                     in integers.  Not in the reference.
+ * Width and height are positive, even and fit u16.
+ * A width that is a multiple of 8 with aligned operands -- source base, pitch and stride to 8 bytes for RGB8, to 16 for the 4-byte formats;
+ * destination base and stride to 8 bytes -- takes 8- / 16-byte non-temporal loads, 8-byte luma and 4-byte chroma stores; anything else a
+ * byte-granular path with the same result.  No atomics, nothing allocated: a call is one kernel node of a recorded graph.  Measured on one
+ * MI355X: see profiles/ingest.md.
+ * PFV_ERR_BAD_ARG: a format or chroma mode that does not exist, a null buffer or context, dimensions a frame cannot have, n_streams <= 0, a
+ * pitch below the row size, a source stride below pitch x height, a destination stride below pfv_frame_bytes, source and destination ranges
+ * that overlap. */
+enum { PFV_CHROMA_POINT = 0, PFV_CHROMA_BOX = 1 };
+/* asynchronous on the context's stream; one k_ingest_rgb */
+PFV_API int pfv_frames_from_rgb_dev(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src_dev, int format, size_t src_pitch,
+                                    size_t src_stride, uint8_t *dst_dev, size_t dst_stride, int chroma);
+/* host buffers: tight pictures in, packed frames out; synchronises; PFV_ERR_STATE while a graph is being recorded */
+PFV_API int pfv_frames_from_rgb(pfv_ctx *ctx, int width, int height, int n_streams, const uint8_t *src, uint8_t *dst, int format, int chroma);
+/* An encoder session's input: the pictures of the slots of the session's current window (slot k's picture at pictures_dev + k * stride) into
+ * slot k's frame of a packed buffer the session owns (n_streams x pfv_frame_bytes), one k_ingest_rgb; *frames_dev_out = that buffer's base.
+ * From that point of the stream on the pointer is a valid `frames_dev` for every session entry point that takes one -- pfv_enc_iframe_dev /
+ * pfv_enc_pframe_dev, the size / RD / SSIM probes, pfv_enc_distortion_dev, pfv_enc_ssim_dev -- indexed by slot as they index it, so one
+ * ingest call serves all of them.  Frames of slots outside the window are left alone.  The buffer is allocated by the first call (which
+ * returns PFV_ERR_STATE inside a graph recording; later calls are recorded as one kernel node) and lives with the session.
+ * PFV_ERR_STATE while a non-zero pfv_enc_session_set_frame_stride is set: the buffer is packed.  GOP-batched input uses the picture
+ * `stride` instead (G x picture bytes). */
+PFV_API int pfv_enc_ingest_rgb_dev(pfv_enc_session *s, const uint8_t *pictures_dev, int format, size_t pitch, size_t stride, int chroma,
+                                   const uint8_t **frames_dev_out);
+/* pfv_encoder: while on, every call that takes (y, u, v) -- encode_iframe, encode_pframe, encode_frame and the six pfv_encoder_probe_* --
+ * takes ONE tight host picture in `format` as y and requires u == v == NULL (anything else: PFV_ERR_BAD_ARG).  The picture goes up once into
+ * device scratch of the encoder (made by this call, never by an encode call) and one k_ingest_rgb puts the frame into the session's frame
+ * staging; the stream, the rungs chosen, frame types, reports and frame SSIM are bit for bit those of an encoder fed the converted planes.
+ * `on` with a bad format or chroma mode: PFV_ERR_BAD_ARG; off ignores the other arguments and the calls are the planar ones again.
+ * pfv_gop_encoder and pfv_batch_encoder have no switch of their own: their _dev forms take frames that pfv_frames_from_rgb_dev made. */
+PFV_API int pfv_encoder_set_input_rgb(pfv_encoder *e, int on, int format, int chroma);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

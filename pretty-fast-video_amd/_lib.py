@@ -38,6 +38,7 @@ PFV_ENC_TRANSFORM_AUTO, PFV_ENC_TRANSFORM_INT = 0, 1
 PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_frames_sse_dev
 PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_deblock / pfv_decoder_set_deblock
 PFV_PIX_RGB8, PFV_PIX_RGBA8, PFV_PIX_BGRA8 = 0, 1, 2             # pixel formats of pfv_frames_to_rgb* and the decoders' RGB outputs
+PFV_CHROMA_POINT, PFV_CHROMA_BOX = 0, 1                          # chroma modes of pfv_frames_from_rgb* and the encoders' RGB inputs
 
 
 class PfvError(RuntimeError):
@@ -179,6 +180,10 @@ SIGNATURES = [
     ("pfv_dec_get_frame_rgb", c_int, [_P, _P, c_int]),
     ("pfv_dec_set_output_rgb_dev", c_int, [_P, _P, c_int, c_size_t, c_size_t]),
     ("pfv_decoder_set_output_rgb", c_int, [_P, c_int, c_int]),
+    ("pfv_frames_from_rgb_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, c_size_t, _P, c_size_t, c_int]),
+    ("pfv_frames_from_rgb", c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int]),
+    ("pfv_enc_ingest_rgb_dev", c_int, [_P, _P, c_int, c_size_t, c_size_t, c_int, _P]),
+    ("pfv_encoder_set_input_rgb", c_int, [_P, c_int, c_int, c_int]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

@@ -93,6 +93,10 @@ struct pfv_encoder {
     int gop_max = 0;                       // pfv_encoder_set_gop: an i-frame is forced once this many frames have followed the last one; 0: never
     uint64_t n_written = 0;                // frames written, drop frames included
     int since_iframe = 0;                  // frames written behind the last i-frame, drop frames included
+    // RGB picture input (pfv_encoder_set_input_rgb): `y` of every call is one tight picture, u and v are NULL
+    bool rgb_on = false;
+    int rgb_format = 0, rgb_chroma = 0;    // PFV_PIX_*, PFV_CHROMA_*
+    uint8_t *rgb_scratch = nullptr;        // device: where the picture waits for k_ingest_rgb; holds any format; made by the set call
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -642,10 +646,24 @@ static void fill_ssim(pfv_encoder *e, int type)
     e->ssim_state = 1;
 }
 
+// the (y, u, v) of an entry point: three planes, or under pfv_encoder_set_input_rgb one picture as y with u == v == NULL
+static bool planes_given(const pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v) { return e->rgb_on ? (y && !u && !v) : (y && u && v); }
+static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v);
+
 static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v)
 {
-    if (!y || !u || !v) return fail(e->ctx, PFV_ERR_BAD_ARG, "null plane");
+    if (!planes_given(e, y, u, v)) return fail(e->ctx, PFV_ERR_BAD_ARG, e->rgb_on ? "RGB input is on: y is the picture, u and v must be NULL" : "null plane");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
+    if (e->rgb_on && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted planes come back down
+        pfv_ctx *ctx = e->ctx;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        int rc = enc_staging(e->hot);
+        if (!rc) rc = upload_planes(e, y, u, v);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(e->frame.data(), e->hot->st_frames, pfv_frame_bytes(e->width, e->height), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return PFV_OK;
+    }
     if (e->device_entropy) {   // the planes go up from where they lie (encode_on_device): no packing copy -- it was half of a 4K frame's time
         e->plane[0] = y; e->plane[1] = u; e->plane[2] = v;
         return PFV_OK;
@@ -683,6 +701,12 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
     pfv_enc_session *s = e->hot;
     pfv_ctx *ctx = e->ctx;
     const size_t ny = (size_t)e->width * e->height, nc = (size_t)(e->width / 2) * (e->height / 2);
+    if (e->rgb_on) {   // the picture up into the encoder's scratch, one k_ingest_rgb into the staging
+        const size_t row = pfv_rgb_row_bytes(e->width, e->rgb_format);
+        hipError_t he = hipMemcpyAsync(e->rgb_scratch, y, row * (size_t)e->height, hipMemcpyHostToDevice, ctx->stream);
+        if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "picture upload"); }
+        return ingest_launch(ctx, e->width, e->height, 1, e->rgb_scratch, e->rgb_format, row, row * (size_t)e->height, s->st_frames, ny + 2 * nc, e->rgb_chroma);
+    }
     const bool packed = u == y + ny && v == u + nc;   // a packed frame: one copy
     hipError_t he = hipMemcpyAsync(s->st_frames, y, packed ? ny + 2 * nc : ny, hipMemcpyHostToDevice, ctx->stream);
     if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny, u, nc, hipMemcpyHostToDevice, ctx->stream);
@@ -728,6 +752,26 @@ PFV_API int pfv_encoder_set_device_entropy(pfv_encoder *e, int on)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     e->device_entropy = on != 0;
+    return PFV_OK;
+}
+
+// RGB picture input: while on, the (y, u, v) of every encode_* / probe_* call is (one tight picture in `format`, NULL, NULL); pack_frame and
+// upload_planes are the two places a frame enters, and the only ones that know (include/pfv_hip_ext.h, "RGB / RGBA picture input")
+PFV_API int pfv_encoder_set_input_rgb(pfv_encoder *e, int on, int format, int chroma)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!on) {
+        e->rgb_on = false;
+        return PFV_OK;
+    }
+    pfv_ctx *ctx = e->ctx;
+    if (!pix_format_ok(format)) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_input_rgb: format must be PFV_PIX_RGB8, _RGBA8 or _BGRA8");
+    if (!chroma_mode_ok(chroma)) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_input_rgb: chroma must be PFV_CHROMA_POINT or PFV_CHROMA_BOX");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = enc_staging(e->hot);
+    if (rc) return rc;
+    if (!e->rgb_scratch) HIP_TRY(ctx, hipMalloc((void **)&e->rgb_scratch, (size_t)e->width * e->height * 4));
+    e->rgb_on = true; e->rgb_format = format; e->rgb_chroma = chroma;
     return PFV_OK;
 }
 
@@ -910,7 +954,7 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
 PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
@@ -921,7 +965,7 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
 PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_rd: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_rd: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
@@ -932,7 +976,7 @@ PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const 
 PFV_API int pfv_encoder_probe_iframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_ssim: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_ssim: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
@@ -954,7 +998,7 @@ static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *
 PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr);
@@ -963,7 +1007,7 @@ PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uin
 PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_rd: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_rd: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out);
@@ -972,7 +1016,7 @@ PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const 
 PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!y || !u || !v || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_ssim: null buffer");
+    if (!planes_given(e, y, u, v) || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_ssim: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out, ssim_q24_out);
@@ -1166,6 +1210,11 @@ PFV_API int pfv_encoder_drain(pfv_encoder *e, const uint8_t **data, size_t *len)
 PFV_API void pfv_encoder_destroy(pfv_encoder *e)
 {
     if (!e) return;
+    if (e->rgb_scratch) {
+        (void)hipSetDevice(e->ctx->device);
+        (void)hipStreamSynchronize(e->ctx->stream);
+        (void)hipFree(e->rgb_scratch);
+    }
     pfv_enc_session_destroy(e->hot);
     delete e;
 }

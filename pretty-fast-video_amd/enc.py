@@ -62,7 +62,27 @@ class Encoder:
         if n.value:
             self.writer.write(ctypes.string_at(data.value, n.value))
 
+    def set_input_rgb(self, on=True, fmt="rgb8", chroma="point"):
+        """the encode_* / probe_* methods take one tight picture instead of a :class:`VideoFrame`: a uint8 array [height, width, 3 or 4] in
+        fmt "rgb8" / "rgba8" / "bgra8"; chroma "point" (the reference's) or "box" (pfv_encoder_set_input_rgb)"""
+        from .quality import chroma_mode, pix_format, rgb_shape
+        m = pix_format(fmt)
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_input_rgb(self.handle, 1 if on else 0, m, chroma_mode(chroma)))
+        self._rgb_shape = rgb_shape(self.ctx, self.width, self.height, m) if on else None
+
+    def _input(self, frame):
+        """the (y, u, v) of a C call: the frame's planes, or under set_input_rgb (picture, NULL, NULL)"""
+        if getattr(self, "_rgb_shape", None):
+            import numpy as np
+            self._picture = np.ascontiguousarray(frame, dtype=np.uint8)        # alive until the call returns
+            assert self._picture.shape == self._rgb_shape, (self._picture.shape, self._rgb_shape)
+            return ptr(self._picture), None, None
+        return ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels), ptr(frame.plane_v.pixels)
+
     def _check_frame(self, frame: VideoFrame):
+        if getattr(self, "_rgb_shape", None):
+            assert not self.finished
+            return
         assert frame.width == self.width and frame.height == self.height                                  # src/enc.rs:76-79
         assert frame.plane_y.width == frame.width and frame.plane_y.height == frame.height
         assert frame.plane_u.width == frame.width // 2 and frame.plane_u.height == frame.height // 2
@@ -71,14 +91,12 @@ class Encoder:
 
     def encode_iframe(self, frame: VideoFrame):
         self._check_frame(frame)
-        self.ctx.check(self.ctx._lib.pfv_encoder_encode_iframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                               ptr(frame.plane_v.pixels)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_encode_iframe(self.handle, *self._input(frame)))
         self._flush()
 
     def encode_pframe(self, frame: VideoFrame):
         self._check_frame(frame)
-        self.ctx.check(self.ctx._lib.pfv_encoder_encode_pframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                               ptr(frame.plane_v.pixels)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_encode_pframe(self.handle, *self._input(frame)))
         self._flush()
 
     def encode_dropframe(self):
@@ -116,8 +134,7 @@ class Encoder:
         import numpy as np
         self._check_frame(frame)
         sizes = np.zeros(self.n_rungs, dtype=np.uint32)
-        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                              ptr(frame.plane_v.pixels), ptr(sizes)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe(self.handle, *self._input(frame), ptr(sizes)))
         return sizes
 
     def set_iframe_quality_floor(self, min_psnr_yuv: float = 0.0):
@@ -132,8 +149,7 @@ class Encoder:
         import numpy as np
         self._check_frame(frame)
         sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
-        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe_rd(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                                 ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_iframe_rd(self.handle, *self._input(frame), ptr(sizes), ptr(sse)))
         return sizes, sse
 
     def probe_pframe(self, frame: VideoFrame):
@@ -141,8 +157,7 @@ class Encoder:
         that rung); the stream, the reference and the rung stay as they are.  PfvError(PFV_ERR_STATE) when poisoned or finished"""
         import numpy as np
         sizes = np.zeros(self.n_rungs, dtype=np.uint32)
-        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                              ptr(frame.plane_v.pixels), ptr(sizes)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe(self.handle, *self._input(frame), ptr(sizes)))
         return sizes
 
     def probe_pframe_rd(self, frame: VideoFrame):
@@ -151,8 +166,7 @@ class Encoder:
         stay as they are.  PfvError(PFV_ERR_STATE) when poisoned or finished"""
         import numpy as np
         sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
-        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe_rd(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                                 ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_probe_pframe_rd(self.handle, *self._input(frame), ptr(sizes), ptr(sse)))
         return sizes, sse
 
     def set_pframe_quality_floor(self, min_psnr_yuv: float = 0.0):
@@ -167,7 +181,7 @@ class Encoder:
         import numpy as np
         sizes, sse = np.zeros(self.n_rungs, dtype=np.uint32), np.zeros((self.n_rungs, 3), dtype=np.uint64)
         q24 = np.zeros((self.n_rungs, 3), dtype=np.int64)
-        self.ctx.check(fn(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels), ptr(frame.plane_v.pixels), ptr(sizes), ptr(sse), ptr(q24)))
+        self.ctx.check(fn(self.handle, *self._input(frame), ptr(sizes), ptr(sse), ptr(q24)))
         return sizes, sse, q24
 
     def probe_iframe_ssim(self, frame: VideoFrame):
@@ -205,8 +219,7 @@ class Encoder:
         """the frame's type chosen by the probes (pfv_encoder_encode_frame, include/pfv_hip_ext.h) -> 1 i-frame, 2 p-frame, 3 drop frame"""
         self._check_frame(frame)
         t = ctypes.c_int(0)
-        self.ctx.check(self.ctx._lib.pfv_encoder_encode_frame(self.handle, ptr(frame.plane_y.pixels), ptr(frame.plane_u.pixels),
-                                                              ptr(frame.plane_v.pixels), ctypes.byref(t)))
+        self.ctx.check(self.ctx._lib.pfv_encoder_encode_frame(self.handle, *self._input(frame), ctypes.byref(t)))
         self._flush()
         return int(t.value)
 
@@ -386,6 +399,9 @@ class GopEncoder(Encoder):
         y, u, v = frame
         assert not self.finished and y.size == self.width * self.height and u.size == v.size == (self.width // 2) * (self.height // 2)
         return ptr(y), ptr(u), ptr(v)
+
+    def set_input_rgb(self, on=True, fmt="rgb8", chroma="point"):
+        raise NotImplementedError("pfv_gop_encoder has no RGB switch: convert with pfv_frames_from_rgb_dev and use its _dev forms")
 
     def encode_iframe(self, frame):
         self.ctx.check(self.ctx._lib.pfv_gop_encoder_encode_iframe(self.handle, *self._planes(frame)))

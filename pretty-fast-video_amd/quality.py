@@ -122,6 +122,29 @@ def frames_to_rgb(ctx: Context, width: int, height: int, frames, fmt="rgb8") -> 
     return out
 
 
+CHROMA_MODES = {"point": _lib.PFV_CHROMA_POINT, "box": _lib.PFV_CHROMA_BOX}
+
+
+def chroma_mode(chroma) -> int:
+    """a chroma mode of the RGB inputs: "point" / "box" or a PFV_CHROMA_* value"""
+    return CHROMA_MODES[chroma.lower()] if isinstance(chroma, str) else int(chroma)
+
+
+def frames_from_rgb(ctx: Context, width: int, height: int, pictures, fmt="rgb8", chroma="point") -> np.ndarray:
+    """tight interleaved pictures (uint8, n pictures of [height, width, 3 or 4]) as packed Y|U|V 4:2:0 frames, uint8 [n, frame bytes]: the
+    reference's load_frame arithmetic (include/pfv_hip_ext.h, "RGB / RGBA picture input"), fmt "rgb8" / "rgba8" / "bgra8", chroma "point"
+    (the reference's: the even pixel's chroma) or "box" (the mean of the 2 x 2 pixels' chroma) (pfv_frames_from_rgb)"""
+    fb = int(ctx._lib.pfv_frame_bytes(int(width), int(height)))
+    m = pix_format(fmt)
+    pic = int(np.prod(rgb_shape(ctx, width, height, m)))
+    p = np.ascontiguousarray(pictures, dtype=np.uint8).reshape(-1)
+    assert fb > 0 and p.size % pic == 0 and p.size
+    n = p.size // pic
+    out = np.empty((n, fb), dtype=np.uint8)
+    ctx.check(ctx._lib.pfv_frames_from_rgb(ctx.handle, int(width), int(height), n, ptr(p), ptr(out), m, chroma_mode(chroma)))
+    return out
+
+
 class FrameSsimStruct(ctypes.Structure):
     """pfv_frame_ssim"""
     _fields_ = [("q24", ctypes.c_int64 * 3), ("windows", ctypes.c_uint32 * 3), ("ssim", ctypes.c_double * 3), ("ssim_all", ctypes.c_double)]

@@ -204,6 +204,16 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_pframe_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(mv_dev),
                                                         ctypes.c_void_p(has_dev), ctypes.c_void_p(coef_dev)))
 
+    def ingest_rgb_dev(self, pictures_dev: int, fmt="rgb8", pitch: int = 0, stride: int = 0, chroma="point") -> int:
+        """asynchronous: the RGB pictures of the window's slots (slot k's at pictures_dev + k * stride, rows `pitch` apart; 0: tight) into
+        slot k's frame of a packed buffer the session owns; returns that buffer's device address, a `frames_dev` for the encode, probe,
+        distortion_dev and ssim_dev calls (pfv_enc_ingest_rgb_dev)"""
+        from .quality import chroma_mode, pix_format
+        out = ctypes.c_void_p()
+        self.ctx.check(self.ctx._lib.pfv_enc_ingest_rgb_dev(self.handle, ctypes.c_void_p(pictures_dev), pix_format(fmt), int(pitch), int(stride),
+                                                            chroma_mode(chroma), ctypes.byref(out)))
+        return int(out.value)
+
     # GOP-batched use: the slots hold the GOPs of one stream (include/pfv_hip.h, pfv_enc_session_set_window) -----------
     def set_frame_stride(self, stride_bytes: int = 0):
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_frame_stride(self.handle, int(stride_bytes)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -29,6 +29,11 @@ it -- pfv_dec_get_frame_dev (k_crop_frames) plus one pfv_yuv420_to_rgb_dev per s
 HIP events around each, warm-up, the median of the samples, a / b / c alternating in three rounds; milliseconds, the bytes each must move
 (picture bytes read + bytes written) over its time, and (a)'s rate as a fraction of (c)'s.  With PFV_HIP_LIB set (another build of the C ABI:
 the CPU emulator) only the small shape runs, twice: the rows are printed, their times mean nothing.
+
+--time-ingest (on the GPU box) adds twelve lines, one per pixel format and chroma mode (point, box) on 96 x 1080p and on one WIDTH x HEIGHT
+stream: planar frames from RGB pictures (a) by pfv_frames_from_rgb_dev -- one k_ingest_rgb; (b) the way without it -- one pfv_rgb_to_yuv420_dev
+per stream, which takes RGB8 and gives POINT only (the same figure beside every format and mode); (c) pfv_frames_to_rgb_dev on the same shape
+and format: the same bytes in the other direction.  Method, units and the PFV_HIP_LIB rule as --time-present; (a)'s rate as a fraction of (c)'s.
 
 --time-kernel (on the GPU box) adds one more line: the k_sse_mb + k_sse_sum pair at the benched shape -- 96 streams of 1920 x 1080,
 input packed, reconstruction padded, map to scratch -- against pfv_dec_get_frame_dev (k_crop_frames) over the same 96 frames, which
@@ -339,6 +344,56 @@ def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=
             "a_present_ms": med["a_present"], "b_crop_plus_per_stream_ms": med["b_crop_plus_per_stream"], "c_crop_ms": med["c_crop"],
             "bytes": moved, "GBps": gbps, "a_over_b_time": over(med["a_present"], med["b_crop_plus_per_stream"]),
             "a_rate_over_c_rate": over(gbps["a_present"], gbps["c_crop"]) if gbps["a_present"] else None, "rounds_ms": res}
+
+
+def time_ingest(pkg, ctx, fmt, chroma, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
+    lib = ctx._lib
+    P = ctypes.c_void_p
+    fb = int(lib.pfv_frame_bytes(w, h))
+    m, c = pkg.quality.pix_format(fmt), pkg.quality.chroma_mode(chroma)
+    bpp = int(lib.pfv_rgb_row_bytes(w, m)) // w
+    f0, planar = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    rgb, rgb3 = ctx.alloc(w * h * bpp * n_streams), ctx.alloc(w * h * 3 * n_streams)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, f0)
+    ctx.check(lib.pfv_frames_to_rgb_dev(ctx.handle, w, h, n_streams, P(f0), 0, 0, P(rgb), m, 0, 0))     # the pictures to ingest, in `fmt` and in RGB8
+    ctx.check(lib.pfv_frames_to_rgb_dev(ctx.handle, w, h, n_streams, P(f0), 0, 0, P(rgb3), 0, 0, 0))
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got), min(got), max(got)
+
+    def without():                                # one launch per stream: RGB8 in, POINT out, whatever `fmt` and `chroma` are
+        for k in range(n_streams):
+            ctx.check(lib.pfv_rgb_to_yuv420_dev(ctx.handle, P(rgb3 + k * w * h * 3), w, h, P(planar + k * fb)))
+    ways = {"a_ingest": lambda: ctx.check(lib.pfv_frames_from_rgb_dev(ctx.handle, w, h, n_streams, P(rgb), m, 0, 0, P(planar), 0, c)),
+            "b_per_stream": without,
+            "c_present": lambda: ctx.check(lib.pfv_frames_to_rgb_dev(ctx.handle, w, h, n_streams, P(f0), 0, 0, P(rgb), m, 0, 0))}
+    res = {k: [] for k in ways}
+    for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
+        for key, fn in ways.items():
+            res[key].append(median_ms(fn))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    for p in (f0, planar, rgb, rgb3):
+        ctx.free(p)
+    med = {k: statistics.median(v for v, _, _ in r) for k, r in res.items()}
+    moved = {"a_ingest": n_streams * (w * h * bpp + fb), "b_per_stream": n_streams * (w * h * 3 + fb), "c_present": n_streams * (fb + w * h * bpp)}
+    over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
+    gbps = {k: over(moved[k], med[k] * 1e6) for k in ways}
+    return {"shape": f"{n_streams} x {w}x{h}", "format": fmt, "chroma": chroma, "samples_per_round": samples, "rounds": rounds,
+            "a_ingest_ms": med["a_ingest"], "b_per_stream_ms": med["b_per_stream"], "c_present_ms": med["c_present"],
+            "bytes": moved, "GBps": gbps, "a_over_b_time": over(med["a_ingest"], med["b_per_stream"]),
+            "a_rate_over_c_rate": over(gbps["a_ingest"], gbps["c_present"]) if gbps["a_ingest"] else None, "rounds_ms": res}
 
 
 def time_kernels(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
@@ -977,6 +1032,7 @@ def main():
     ap.add_argument("--dump", default=None)
     ap.add_argument("--time-deblock", action="store_true")
     ap.add_argument("--time-present", action="store_true")
+    ap.add_argument("--time-ingest", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -996,6 +1052,13 @@ def main():
                 for fmt in ("rgb8", "rgba8", "bgra8"):
                     kw = dict(warmup=1, samples=2, rounds=1) if emu else {}
                     print(json.dumps({"time_present": time_present(pkg, ctx, fmt, **shape, **kw)}), flush=True)
+        if a.time_ingest:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the rows only
+            for shape in ([] if emu else [dict(n_streams=96, w=1920, h=1080)]) + [dict(n_streams=1, w=a.width, h=a.height)]:
+                for fmt in ("rgb8", "rgba8", "bgra8"):
+                    for chroma in ("point", "box"):
+                        kw = dict(warmup=1, samples=2, rounds=1) if emu else {}
+                        print(json.dumps({"time_ingest": time_ingest(pkg, ctx, fmt, chroma, **shape, **kw)}), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
         if a.probe:
