@@ -158,6 +158,60 @@ inline std::vector<uint8_t> frames_from_rgb(Context &ctx, size_t width, size_t h
 }
 
 // src/enc.rs:12-188
+// frame resize (include/pfv_hip_ext.h, "frame resize"): the filter kinds, one axis' table, the plan object and the host-buffer form
+enum class ScaleKind { Bilinear = PFV_SCALE_BILINEAR, Bicubic = PFV_SCALE_BICUBIC, Lanczos3 = PFV_SCALE_LANCZOS3 };
+inline int scale_taps(ScaleKind kind, size_t n_src, size_t n_dst) { return pfv_scale_taps((int)kind, (int)n_src, (int)n_dst); }
+struct ScaleTable {
+    int taps = 0;
+    std::vector<int32_t> first;   // [n_dst]
+    std::vector<int16_t> coef;    // [n_dst][taps]: every row sums to 16384
+};
+inline ScaleTable scale_table(ScaleKind kind, size_t n_src, size_t n_dst)
+{
+    ScaleTable t;
+    t.taps = scale_taps(kind, n_src, n_dst);
+    if (!t.taps) throw Error(PFV_ERR_BAD_ARG, "scale_table: a kind that does not exist, a size outside 1 .. 65535 or a reduction beyond 8");
+    t.first.resize(n_dst);
+    t.coef.resize(n_dst * (size_t)t.taps);
+    const int rc = pfv_scale_table((int)kind, (int)n_src, (int)n_dst, t.first.data(), t.coef.data());
+    if (rc != PFV_OK) throw Error(rc, pfv_last_error(nullptr));
+    return t;
+}
+// pfv_scaler: the four tables of one (source size, destination size, kind) on the device; destroy it before its context
+class Scaler {
+  public:
+    Scaler(Context &ctx, size_t sw, size_t sh, size_t dw, size_t dh, ScaleKind kind) : ctx_(ctx), sw_(sw), sh_(sh), dw_(dw), dh_(dh)
+    {
+        int rc = PFV_OK;
+        h_ = pfv_scaler_create(ctx.handle(), (int)sw, (int)sh, (int)dw, (int)dh, (int)kind, &rc);
+        if (!h_) ctx_.check(rc ? rc : PFV_ERR_BAD_ARG);
+    }
+    ~Scaler() { pfv_scaler_destroy(h_); }
+    Scaler(const Scaler &) = delete;
+    Scaler &operator=(const Scaler &) = delete;
+    pfv_scaler *handle() const { return h_; }
+    size_t src_frame_bytes() const { return pfv_frame_bytes((int)sw_, (int)sh_); }
+    size_t dst_frame_bytes() const { return pfv_frame_bytes((int)dw_, (int)dh_); }
+    // asynchronous on the context's stream, one k_scale: device frames in (packed or padded, src_stride apart), packed device frames out
+    void run_dev(int n_streams, const uint8_t *src_dev, uint8_t *dst_dev, int src_layout = PFV_FRAME_PACKED, size_t src_stride = 0, size_t dst_stride = 0)
+    {
+        ctx_.check(pfv_scaler_run_dev(h_, n_streams, src_dev, src_layout, src_stride, dst_dev, dst_stride));
+    }
+
+  private:
+    Context &ctx_;
+    size_t sw_, sh_, dw_, dh_;
+    pfv_scaler *h_ = nullptr;
+};
+inline std::vector<uint8_t> frames_scale(Context &ctx, size_t sw, size_t sh, size_t dw, size_t dh, const std::vector<uint8_t> &frames, ScaleKind kind)
+{
+    const size_t sfb = pfv_frame_bytes((int)sw, (int)sh), dfb = pfv_frame_bytes((int)dw, (int)dh);
+    if (!sfb || !dfb || frames.empty() || frames.size() % sfb) throw std::invalid_argument("frames_scale: frames must hold whole packed frames of the source size");
+    std::vector<uint8_t> out(frames.size() / sfb * dfb);
+    ctx.check(pfv_frames_scale(ctx.handle(), (int)sw, (int)sh, (int)dw, (int)dh, (int)(frames.size() / sfb), frames.data(), out.data(), (int)kind));
+    return out;
+}
+
 class Encoder {
   public:
     Encoder(std::ostream &writer, size_t width, size_t height, uint32_t framerate, int quality, Context &ctx)
@@ -213,7 +267,16 @@ class Encoder {
     void set_input_rgb(bool on, PixelFormat format = PixelFormat::Rgb8, ChromaMode chroma = ChromaMode::Point)
     {
         ctx_.check(pfv_encoder_set_input_rgb(h_, on ? 1 : 0, (int)format, (int)chroma));
-        rgb_bytes_ = on ? rgb_row_bytes(width_, format) * height_ : 0;
+        rgb_bytes_ = on ? rgb_row_bytes(in_w_, format) * in_h_ : 0;
+    }
+    // frames -- under set_input_rgb pictures -- of src_width x src_height, resized on the device to the encoder's size; src_width 0: off
+    void set_input_size(size_t src_width, size_t src_height, ScaleKind kind = ScaleKind::Bicubic)
+    {
+        ctx_.check(pfv_encoder_set_input_size(h_, (int)src_width, (int)src_height, (int)kind));
+        const size_t bpp = rgb_bytes_ / (in_w_ * in_h_);
+        in_w_ = src_width ? src_width : width_;
+        in_h_ = src_width ? src_height : height_;
+        rgb_bytes_ = bpp * in_w_ * in_h_;
     }
     void encode_iframe_rgb(const std::vector<uint8_t> &picture)
     {
@@ -359,8 +422,8 @@ class Encoder {
     void check_frame(const VideoFrame &f) const   // the asserts of src/enc.rs:76-80
     {
         if (rgb_bytes_) throw std::logic_error("Encoder: the encoder takes RGB pictures (set_input_rgb): use the _rgb methods");
-        if (f.width != width_ || f.height != height_ || f.plane_y.pixels.size() != width_ * height_ ||
-            f.plane_u.pixels.size() != (width_ / 2) * (height_ / 2) || f.plane_v.pixels.size() != (width_ / 2) * (height_ / 2))
+        if (f.width != in_w_ || f.height != in_h_ || f.plane_y.pixels.size() != in_w_ * in_h_ ||
+            f.plane_u.pixels.size() != (in_w_ / 2) * (in_h_ / 2) || f.plane_v.pixels.size() != (in_w_ / 2) * (in_h_ / 2))
             throw std::invalid_argument("Encoder: frame geometry does not match the encoder (src/enc.rs:76-79)");
     }
     void flush()
@@ -374,6 +437,7 @@ class Encoder {
     Context &ctx_;
     std::ostream &out_;
     size_t width_, height_;
+    size_t in_w_ = width_, in_h_ = height_;   // the size of what the encode calls take: set_input_size's, else the encoder's
     size_t rgb_bytes_ = 0;          // set_input_rgb: the size of one picture; 0 while the switch is off
     bool finished_ = false;
     pfv_encoder *h_ = nullptr;
@@ -410,7 +474,17 @@ class Decoder {
     void set_output_rgb(bool on, PixelFormat format = PixelFormat::Rgb8)
     {
         ctx_.check(pfv_decoder_set_output_rgb(h_, on ? 1 : 0, (int)format));
-        rgb_bytes_ = on ? rgb_row_bytes(width(), format) * height() : 0;
+        rgb_bytes_ = on ? rgb_row_bytes(out_w_ ? out_w_ : width(), format) * (out_w_ ? out_h_ : height()) : 0;
+    }
+    // every frame -- under set_output_rgb every picture -- resized on the device to out_width x out_height; out_width 0: off.  width() and
+    // height() keep the stream's size; the callback's frame carries its own
+    void set_output_size(size_t out_width, size_t out_height, ScaleKind kind = ScaleKind::Bicubic)
+    {
+        ctx_.check(pfv_decoder_set_output_size(h_, (int)out_width, (int)out_height, (int)kind));
+        const size_t w0 = out_w_ ? out_w_ : width(), h0 = out_w_ ? out_h_ : height(), bpp = rgb_bytes_ / (w0 * h0);
+        out_w_ = out_width;
+        out_h_ = out_width ? out_height : 0;
+        rgb_bytes_ = bpp * (out_w_ ? out_w_ * out_h_ : (size_t)width() * height());
     }
     bool advance_frame_rgb(const OnPicture &onpicture)
     {
@@ -457,6 +531,7 @@ class Decoder {
     {
         Decoder *d = static_cast<Decoder *>(user);
         const size_t ny = (size_t)w * h, nc = (size_t)(w / 2) * (h / 2);
+        if (d->frame_.width != (size_t)w || d->frame_.height != (size_t)h) d->frame_ = VideoFrame((size_t)w, (size_t)h);   // set_output_size
         d->frame_.plane_y.pixels.assign(y, y + ny);
         d->frame_.plane_u.pixels.assign(u, u + nc);
         d->frame_.plane_v.pixels.assign(v, v + nc);
@@ -469,6 +544,7 @@ class Decoder {
     const OnVideo *cb_ = nullptr;
     std::vector<uint8_t> picture_;  // set_output_rgb: the picture the callback sees
     size_t rgb_bytes_ = 0;          // its size; 0 while the switch is off
+    size_t out_w_ = 0, out_h_ = 0;  // set_output_size; 0 while the switch is off
     const OnPicture *pic_cb_ = nullptr;
 };
 

@@ -504,6 +504,87 @@ PFV_API int pfv_enc_ingest_rgb_dev(pfv_enc_session *s, const uint8_t *pictures_d
  * pfv_gop_encoder and pfv_batch_encoder have no switch of their own: their _dev forms take frames that pfv_frames_from_rgb_dev made. */
 PFV_API int pfv_encoder_set_input_rgb(pfv_encoder *e, int on, int format, int chroma);
 
+/* ------------------------------------------------------------------ frame resize  [B]
+ * A frame sw x sh becomes a frame dw x dh without leaving the device: renditions of one source, thumbnails, a render-target size.  (The only
+ * other resampling here, pfv_reduce_dev / pfv_double_dev, is the reference's point-sampled 2x pair, src/common.rs:523-556: one plane, one
+ * ratio, aliasing by construction.)  One launch, k_scale (csrc/pfv_scale_kernels.hip), resizes n_streams frames, all three planes.
+ * Arithmetic (normative).
+ * Planes: all four sizes are positive, even and fit u16.  Each plane is resampled on its own by the same rule -- Y from sw x sh to dw x dh,
+ * U and V from sw/2 x sh/2 to dw/2 x dh/2; chroma is treated as a centre-aligned plane like luma.  The filter is separable: per axis it maps
+ * n_src samples to n_dst samples with a table.
+ *   kind                  S   kernel K(t), a = |t|
+ *   PFV_SCALE_BILINEAR    1   max(0, 1 - a)
+ *   PFV_SCALE_BICUBIC     2   Catmull-Rom: a < 1: (1.5a - 2.5)*a*a + 1;  a < 2: ((-0.5a + 2.5)*a - 4)*a + 2;  else 0
+ *   PFV_SCALE_LANCZOS3    3   K(0) = 1;  a < 3: sinc(pi*a) * sinc(pi*a / 3) with sinc(x) = sin(x) / x;  else 0
+ * Table of one axis, built on the host in IEEE double, every operation rounded on its own (no fused multiply-add), expressions as written:
+ *   m = max(n_src, n_dst);  f = n_src > n_dst ? n_src / n_dst : 1.0;  taps T = n_src > n_dst ? 2 * ceil(S * n_src / n_dst) : 2 * S (the
+ *   ceiling in integers).  For the output index o, in exact integers: num = (2o + 1) * n_src - n_dst and
+ *   first[o] = floor((num - 2 * S * m) / (2 * n_dst)) + 1, floor toward minus infinity.  Centre c = num / (2.0 * n_dst); weights
+ *   w_k = K(((first[o] + k) - c) / f) for k = 0 .. T-1; their sum taken in that order, starting from w_0; q_k = rint(w_k / sum * 16384), ties
+ *   to even; then 16384 - sum(q) is added to the tap of largest |q_k|, the first one on a tie.  Every row sums to exactly 16384.  Coefficients
+ *   are int16, first is int32 and may be negative or reach past the end.  A row whose sum of |q_k| reaches 65536, or a coefficient outside
+ *   int16, makes table creation return PFV_ERR_BAD_ARG; no size pair within the ratio limit is known to get there (the largest sum met over
+ *   source sizes 2 .. 199 is 25 440, and 32767 * 25440 < 2^31: the sums below cannot leave i32).
+ * Ratio limit: T <= 48, that is n_src <= 8 * n_dst on every axis of every plane; a larger reduction returns PFV_ERR_BAD_ARG and the caller
+ * chains two calls.  Upscaling is limited only by u16.
+ * Pixels: all values are i32, >> is an arithmetic shift (floor); indices are clamped to the PICTURE, 0 .. n_src-1, never to the padding of a
+ * padded source:
+ *   t[y][X]   = clamp((sum_k cx[X][k] * src[y][clampx(firstx[X] + k)] + 64) >> 7, -32768, 32767)        horizontal, every source row y
+ *   out[Y][X] = clamp((sum_k cy[Y][k] * t[clampy(firsty[Y] + k)][X] + (1 << 20)) >> 21, 0, 255)          vertical
+ * dw x dh == sw x sh reproduces the source byte for byte under all three kinds; a constant plane stays constant at every ratio.
+ * Source: PACKED or PADDED frames with their own stream stride (the layout argument of pfv_frames_sse_dev), so a decoder session's
+ * framebuffer is read where it lies.  Destination: PACKED frames dst_stride bytes apart (0 = pfv_frame_bytes(dw, dh)); exactly the
+ * destination frames' bytes are written.  Both passes run in the one launch: a workgroup owns a 64 x 16 output tile, filters the source rows
+ * it needs horizontally into LDS as 16-bit values and runs the vertical pass out of LDS -- no intermediate plane in HBM, no atomics, nothing
+ * allocated by a run: a run is one kernel node of a recorded graph.  Planes whose rows all start on 4-byte boundaries (base, stream stride,
+ * plane offset, row pitch) are read / written as dwords (non-temporal stores); anything else takes a byte-granular path with the same result.
+ * PFV_ERR_BAD_ARG: a null pointer, n_streams <= 0, a kind or layout that does not exist, dimensions that are odd, non-positive or beyond
+ * u16, a ratio beyond 8, strides below the frame size, source and destination ranges that overlap.
+ * pfv_gop_* and pfv_batch_* objects have no switch: their _dev forms take frames that pfv_scaler_run_dev made. */
+enum { PFV_SCALE_BILINEAR = 0, PFV_SCALE_BICUBIC = 1, PFV_SCALE_LANCZOS3 = 2 };
+typedef struct pfv_scaler pfv_scaler;
+PFV_API int pfv_scale_taps(int kind, int n_src, int n_dst);                  /* T, or 0 for bad arguments / a ratio beyond 8 */
+/* host, no context: n_dst firsts, n_dst x T coefficients */
+PFV_API int pfv_scale_table(int kind, int n_src, int n_dst, int32_t *first, int16_t *coef);
+/* builds and uploads the four tables (luma x, luma y, chroma x, chroma y); NULL and *err on failure (err may be NULL); PFV_ERR_STATE inside a
+ * graph recording.  The scaler belongs to the context and must be destroyed before it. */
+PFV_API pfv_scaler *pfv_scaler_create(pfv_ctx *ctx, int sw, int sh, int dw, int dh, int kind, int *err);
+PFV_API void pfv_scaler_destroy(pfv_scaler *sc);
+/* asynchronous on the context's stream; one k_scale */
+PFV_API int pfv_scaler_run_dev(pfv_scaler *sc, int n_streams, const uint8_t *src_dev, int src_layout, size_t src_stride, uint8_t *dst_dev,
+                               size_t dst_stride);
+/* host buffers: packed frames in, packed frames out; makes its tables, synchronises; PFV_ERR_STATE while a graph is being recorded */
+PFV_API int pfv_frames_scale(pfv_ctx *ctx, int sw, int sh, int dw, int dh, int n_streams, const uint8_t *src, uint8_t *dst, int kind);
+/* A decoder session's resized frames: an output IN ADDITION to the planar and RGB ones, exactly as pfv_dec_set_output_rgb_dev is.  While set,
+ * every pfv_dec_iframe* / pfv_dec_pframe* call (dense, sparse, lists) also writes the resized frames of the slots of its window, indexed by
+ * slot (slot k's frame at dst_dev + k * stride; stride 0 = pfv_frame_bytes of the destination size), in one k_scale from the new current
+ * framebuffer -- with pfv_dec_set_deblock on from the filtered picture, taken from the planar output or from the session's scratch under the
+ * RGB output's rule (one k_deblock serves both outputs; the scratch is made by the set calls, never by a decode call).  dst_dev NULL switches
+ * it off.  The framebuffer and all other outputs stay bit for bit unchanged.  The scaler's source size must be the session's and its context
+ * the session's, else PFV_ERR_BAD_ARG; the session does not own the scaler, which must outlive the setting. */
+PFV_API int pfv_dec_set_output_scaled_dev(pfv_dec_session *s, pfv_scaler *sc, uint8_t *dst_dev, size_t stride);
+/* pfv_decoder: w != 0: the callback's y, u, v point to the planes of ONE packed w x h frame (u == y + w*h, v == u + (w/2)*(h/2)), the decoded
+ * -- and, if switched on, deblocked -- frame resized with `kind`, and its width / height arguments are w and h; on the host, or on the device
+ * under pfv_decoder_set_output_device(1).  With pfv_decoder_set_output_rgb also on, the picture is the conversion of that resized frame:
+ * k_scale, then k_present_rgb from the packed result.  pfv_decoder_width / _height keep reporting the stream's size.  w == 0 switches it off
+ * (h and kind are then ignored).  Scratch is created by the set calls, never by an advance call.  Results, order and errors of the advance calls
+ * are unchanged. */
+PFV_API int pfv_decoder_set_output_size(pfv_decoder *d, int w, int h, int kind);
+/* An encoder session's input, the mirror of pfv_enc_ingest_rgb_dev: the source frames (packed, of the scaler's source size) of the slots of the
+ * session's current window -- slot k's at frames_dev + k * src_stride, 0 = pfv_frame_bytes of the source size -- are resized into slot k's
+ * frame of a packed buffer the session owns (n_streams x pfv_frame_bytes), one k_scale; *frames_dev_out = that buffer's base, from that point
+ * of the stream on a valid `frames_dev` for every session entry point that takes one.  Frames of slots outside the window are left alone.  The
+ * buffer is a second one beside pfv_enc_ingest_rgb_dev's, allocated by the first call (PFV_ERR_STATE inside a graph recording; later calls
+ * are recorded as one kernel node).  PFV_ERR_STATE while a non-zero pfv_enc_session_set_frame_stride is set.  The scaler's destination size
+ * must be the session's and its context the session's, else PFV_ERR_BAD_ARG. */
+PFV_API int pfv_enc_scale_dev(pfv_enc_session *s, pfv_scaler *sc, const uint8_t *frames_dev, size_t src_stride, const uint8_t **frames_dev_out);
+/* pfv_encoder: src_w != 0: every call that takes (y, u, v) -- encode_iframe, encode_pframe, encode_frame and the six pfv_encoder_probe_* --
+ * takes planes of the size src_w x src_h; they go up once into device scratch of the encoder (made by this call) and one k_scale puts the frame
+ * into the session's frame staging.  With pfv_encoder_set_input_rgb also on, the picture is of the source size: it is ingested into that
+ * scratch and scaled from there.  The stream, the rungs chosen, frame types, reports and frame SSIM are bit for bit those of an encoder fed
+ * the frames that pfv_frames_scale made.  src_w == 0 switches it off (src_h and kind are then ignored). */
+PFV_API int pfv_encoder_set_input_size(pfv_encoder *e, int src_w, int src_h, int kind);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

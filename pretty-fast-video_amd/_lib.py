@@ -39,6 +39,7 @@ PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_
 PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_deblock / pfv_decoder_set_deblock
 PFV_PIX_RGB8, PFV_PIX_RGBA8, PFV_PIX_BGRA8 = 0, 1, 2             # pixel formats of pfv_frames_to_rgb* and the decoders' RGB outputs
 PFV_CHROMA_POINT, PFV_CHROMA_BOX = 0, 1                          # chroma modes of pfv_frames_from_rgb* and the encoders' RGB inputs
+PFV_SCALE_BILINEAR, PFV_SCALE_BICUBIC, PFV_SCALE_LANCZOS3 = 0, 1, 2   # filter kinds of pfv_scaler_create / pfv_frames_scale
 
 
 class PfvError(RuntimeError):
@@ -184,6 +185,16 @@ SIGNATURES = [
     ("pfv_frames_from_rgb", c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int]),
     ("pfv_enc_ingest_rgb_dev", c_int, [_P, _P, c_int, c_size_t, c_size_t, c_int, _P]),
     ("pfv_encoder_set_input_rgb", c_int, [_P, c_int, c_int, c_int]),
+    ("pfv_scale_taps", c_int, [c_int, c_int, c_int]),
+    ("pfv_scale_table", c_int, [c_int, c_int, c_int, _P, _P]),
+    ("pfv_scaler_create", _P, [_P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    ("pfv_scaler_destroy", None, [_P]),
+    ("pfv_scaler_run_dev", c_int, [_P, c_int, _P, c_int, c_size_t, _P, c_size_t]),
+    ("pfv_frames_scale", c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int]),
+    ("pfv_dec_set_output_scaled_dev", c_int, [_P, _P, _P, c_size_t]),
+    ("pfv_decoder_set_output_size", c_int, [_P, c_int, c_int, c_int]),
+    ("pfv_enc_scale_dev", c_int, [_P, _P, _P, c_size_t, _P]),
+    ("pfv_encoder_set_input_size", c_int, [_P, c_int, c_int, c_int]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

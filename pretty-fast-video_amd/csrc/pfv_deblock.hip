@@ -91,7 +91,7 @@ PFV_API int pfv_dec_set_deblock(pfv_dec_session *s, int mode, const uint8_t stre
             if (strength[i] > kDeblockMaxS) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_dec_set_deblock: strength above 12");
         for (int i = 0; i < 3; i++) s->db_fixed[i] = strength[i];
     }
-    if (mode != PFV_DEBLOCK_OFF && s->rgb_out) {   // the RGB output then takes the filtered picture from the session's scratch: made here, never in a decode call
+    if (mode != PFV_DEBLOCK_OFF && (s->rgb_out || s->scaled_out)) {   // the RGB / resized output then takes the filtered picture from the session's scratch: made here, never in a decode call
         const int rc = dec_present_scratch(s, "pfv_dec_set_deblock");
         if (rc) return rc;
     }

@@ -211,11 +211,17 @@ static void dec_stop_workers(pfv_decoder *d)
 static int dec_rgb_buffers(pfv_decoder *d)
 {
     pfv_ctx *ctx = d->ctx;
-    const size_t bytes = (size_t)d->width * d->height * 4;   // holds any format
+    // the picture has the size of the frame it is made from: the resized one while pfv_decoder_set_output_size is on -- and is then made in
+    // device memory on either output path (k_present_rgb from the packed resized frame)
+    const size_t bytes = (d->scaler ? (size_t)d->out_w * d->out_h : (size_t)d->width * d->height) * 4;   // holds any format
+    const bool dev_pic = d->rgb_on && (d->frame_dev || d->scaler);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (d->rgb_on && !d->frame_dev && !d->rgbframe.resize(bytes)) return fail(ctx, PFV_ERR_NOMEM, "pfv_decoder_set_output_rgb: pinned staging");
-    if (d->rgb_on && d->frame_dev && !d->rgb_dev) HIP_TRY(ctx, hipMalloc((void **)&d->rgb_dev, bytes));
-    if (!(d->rgb_on && d->frame_dev) && d->rgb_dev) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(d->rgb_dev); d->rgb_dev = nullptr; }
+    if (d->rgb_dev && (!dev_pic || d->rgb_dev_cap < bytes)) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(d->rgb_dev); d->rgb_dev = nullptr; d->rgb_dev_cap = 0; }
+    if (dev_pic && !d->rgb_dev) {
+        HIP_TRY(ctx, hipMalloc((void **)&d->rgb_dev, bytes));
+        d->rgb_dev_cap = bytes;
+    }
     return PFV_OK;
 }
 
@@ -245,6 +251,8 @@ PFV_API void pfv_decoder_destroy(pfv_decoder *d)
     if (d->win_stream) { (void)hipStreamSynchronize(d->win_stream); (void)hipStreamDestroy(d->win_stream); }
     if (d->frame_dev) (void)hipFree(d->frame_dev);
     if (d->rgb_dev) (void)hipFree(d->rgb_dev);
+    if (d->scaled_dev) (void)hipFree(d->scaled_dev);
+    pfv_scaler_destroy(d->scaler);
     for (DecWindow &w : d->win) w.destroy();
     pfv_dec_session_destroy(d->hot);
     delete d;
@@ -274,7 +282,32 @@ PFV_API int pfv_decoder_set_output_rgb(pfv_decoder *d, int on, int format)
 PFV_API int pfv_decoder_set_deblock(pfv_decoder *d, int mode, const uint8_t strength[3])
 {
     if (!d) return fail(nullptr, PFV_ERR_BAD_ARG, "null decoder");
-    return pfv_dec_set_deblock(d->hot, mode, strength);
+    const int rc = pfv_dec_set_deblock(d->hot, mode, strength);
+    if (rc || mode == PFV_DEBLOCK_OFF || !d->scaler) return rc;
+    return dec_present_scratch(d->hot, "pfv_decoder_set_deblock");   // the filtered picture waits there for k_scale: made here, never by an advance call
+}
+// w != 0: the callback's y, u, v point to the planes of ONE packed w x h frame, the decoded frame resized (kind: PFV_SCALE_*), and its width and
+// height arguments are w and h; with pfv_decoder_set_output_rgb on, y is the picture of that resized frame.  In host memory, or in device memory
+// under pfv_decoder_set_output_device(1).  w == 0 switches it off.  All scratch is made here.
+PFV_API int pfv_decoder_set_output_size(pfv_decoder *d, int w, int h, int kind)
+{
+    if (!d) return fail(nullptr, PFV_ERR_BAD_ARG, "null decoder");
+    pfv_ctx *ctx = d->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    pfv_scaler *sc = nullptr;
+    int rc = PFV_OK;
+    if (w != 0 && !(sc = pfv_scaler_create(ctx, d->width, d->height, w, h, kind, &rc))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // nothing reads the old tables or frame any more
+    pfv_scaler_destroy(d->scaler);
+    if (d->scaled_dev) { (void)hipFree(d->scaled_dev); d->scaled_dev = nullptr; }
+    d->scaler = sc;
+    d->out_w = sc ? w : 0; d->out_h = sc ? h : 0;
+    if (sc) {
+        HIP_TRY(ctx, hipMalloc((void **)&d->scaled_dev, pfv_frame_bytes(w, h)));
+        if (!d->scaledframe.resize(pfv_frame_bytes(w, h))) return fail(ctx, PFV_ERR_NOMEM, "pfv_decoder_set_output_size: pinned staging");
+        if (d->hot->db_mode && (rc = dec_present_scratch(d->hot, "pfv_decoder_set_output_size"))) return rc;
+    }
+    return dec_rgb_buffers(d);
 }
 PFV_API void pfv_decoder_entropy_counts(const pfv_decoder *d, long counts_out[2])
 {
@@ -433,7 +466,17 @@ PFV_API int pfv_decoder_advance_frame(pfv_decoder *d, pfv_video_cb onvideo, void
             rc = e->type == 1 ? pfv_dec_iframe_sparse(d->hot, e->idx.data(), e->val.data(), e->n_sparse, e->qidx)
                               : pfv_dec_pframe_sparse(d->hot, e->mv.data(), e->has.data(), e->idx.data(), e->val.data(),
                                                       e->n_sparse, e->qidx);
-        if (!rc && d->rgb_on) {      // pfv_decoder_set_output_rgb: one picture instead of the planes, on either side
+        if (!rc && d->scaler) {      // pfv_decoder_set_output_size: one k_scale from what pfv_dec_get_frame_dev would return, then the picture of that frame if asked for
+            const size_t fb = pfv_frame_bytes(d->out_w, d->out_h), pic = pfv_rgb_row_bytes(d->out_w, d->rgb_format) * (size_t)d->out_h;
+            rc = dec_scaled_win(d->hot, d->scaler, 0, 1, nullptr, 0, d->scaled_dev, fb);
+            if (!rc && d->rgb_on) rc = pfv_frames_to_rgb_dev(d->ctx, d->out_w, d->out_h, 1, d->scaled_dev, PFV_FRAME_PACKED, 0, d->rgb_dev, d->rgb_format, 0, 0);
+            if (!rc && !d->frame_dev) {
+                const hipError_t he = d->rgb_on ? hipMemcpyAsync(d->rgbframe.data(), d->rgb_dev, pic, hipMemcpyDeviceToHost, d->ctx->stream)
+                                                : hipMemcpyAsync(d->scaledframe.data(), d->scaled_dev, fb, hipMemcpyDeviceToHost, d->ctx->stream);
+                if (he != hipSuccess) rc = hip_fail(d->ctx, he, "download of the resized frame");
+            }
+            if (!rc) rc = pfv_ctx_sync(d->ctx);
+        } else if (!rc && d->rgb_on) {      // pfv_decoder_set_output_rgb: one picture instead of the planes, on either side
             if (d->frame_dev) {
                 rc = pfv_dec_get_frame_rgb_dev(d->hot, d->rgb_dev, d->rgb_format, 0, 0);
                 if (!rc) rc = pfv_ctx_sync(d->ctx);
@@ -455,7 +498,11 @@ PFV_API int pfv_decoder_advance_frame(pfv_decoder *d, pfv_video_cb onvideo, void
     lk.unlock();
     if (rc) return rc;
     if (kind == DecEvent::FRAME && onvideo && d->rgb_on) {
-        onvideo(user, d->frame_dev ? d->rgb_dev : d->rgbframe.data(), nullptr, nullptr, d->width, d->height);
+        onvideo(user, d->frame_dev ? d->rgb_dev : d->rgbframe.data(), nullptr, nullptr, d->scaler ? d->out_w : d->width, d->scaler ? d->out_h : d->height);
+    } else if (kind == DecEvent::FRAME && onvideo && d->scaler) {
+        const size_t ny = (size_t)d->out_w * d->out_h, nc = (size_t)(d->out_w / 2) * (d->out_h / 2);
+        const uint8_t *f = d->frame_dev ? d->scaled_dev : d->scaledframe.data();
+        onvideo(user, f, f + ny, f + ny + nc, d->out_w, d->out_h);
     } else if (kind == DecEvent::FRAME && onvideo) {
         size_t ny = (size_t)d->width * d->height, nc = (size_t)(d->width / 2) * (d->height / 2);
         const uint8_t *f = d->frame_dev ? d->frame_dev : d->retframe.data();

@@ -51,34 +51,58 @@ static int dec_present_scratch(pfv_dec_session *s, const char *what)
     return PFV_OK;
 }
 
-// Slots [first, first + count) of a decoder session as RGB pictures, from what pfv_dec_get_frame_dev would return now.  Deblocking off: the
-// padded framebuffer, read where it lies.  On: the filtered packed frames -- `filtered` (frames `filtered_stride` apart, indexed by slot) when
-// the caller has just produced them, else one k_deblock into the session's scratch first.
+// Slots [first, first + count) of a decoder session as an operand (*g with n_streams = count), holding what pfv_dec_get_frame_dev would return
+// now.  Deblocking off: the padded framebuffer, read where it lies.  On: the filtered packed frames -- `filtered` (frames `filtered_stride`
+// apart, indexed by slot) when the caller has just produced them, else one k_deblock into the session's scratch first.
+static int dec_shown_operand(pfv_dec_session *s, int first, int count, const uint8_t *filtered, size_t filtered_stride, FrameGeom *g, SseOperand *src)
+{
+    *g = s->geom;
+    g->n_streams = count;
+    const size_t fb = (size_t)g->src_frame_bytes;
+    if (!s->db_mode) {
+        *src = sse_operand(*g, s->fb[s->cur] + (size_t)first * (size_t)g->pad_frame_bytes, PFV_FRAME_PADDED, 0);
+    } else if (filtered) {
+        const size_t fs = filtered_stride ? filtered_stride : fb;
+        *src = sse_operand(*g, filtered + (size_t)first * fs, PFV_FRAME_PACKED, fs);
+    } else {
+        if (!s->db_scratch) return fail(s->ctx, PFV_ERR_STATE, "RGB / resized output of a deblocked picture: the session's scratch is missing");
+        const int rc = dec_deblock_win(s, first, count, s->db_scratch, 0);
+        if (rc) return rc;
+        *src = sse_operand(*g, s->db_scratch + (size_t)first * fb, PFV_FRAME_PACKED, 0);
+    }
+    return PFV_OK;
+}
+// ... as RGB pictures
 static int dec_present_win(pfv_dec_session *s, int first, int count, const uint8_t *filtered, size_t filtered_stride, uint8_t *dst, int format, size_t pitch,
                            size_t stride)
 {
-    pfv_ctx *ctx = s->ctx;
-    FrameGeom g = s->geom;
-    g.n_streams = count;
-    const size_t fb = (size_t)g.src_frame_bytes;
+    FrameGeom g;
     SseOperand src;
-    if (!s->db_mode) {
-        src = sse_operand(g, s->fb[s->cur] + (size_t)first * (size_t)g.pad_frame_bytes, PFV_FRAME_PADDED, 0);
-    } else if (filtered) {
-        const size_t fs = filtered_stride ? filtered_stride : fb;
-        src = sse_operand(g, filtered + (size_t)first * fs, PFV_FRAME_PACKED, fs);
-    } else {
-        if (!s->db_scratch) return fail(ctx, PFV_ERR_STATE, "RGB output of a deblocked picture: the session's scratch is missing");
-        const int rc = dec_deblock_win(s, first, count, s->db_scratch, 0);
-        if (rc) return rc;
-        src = sse_operand(g, s->db_scratch + (size_t)first * fb, PFV_FRAME_PACKED, 0);
-    }
-    return present_launch(ctx, g, src, dst + (size_t)first * stride, format, pitch, stride);
+    const int rc = dec_shown_operand(s, first, count, filtered, filtered_stride, &g, &src);
+    if (rc) return rc;
+    return present_launch(s->ctx, g, src, dst + (size_t)first * stride, format, pitch, stride);
 }
-// the decode calls' share (dec_step): the window's pictures into the output of pfv_dec_set_output_rgb_dev
+// ... as frames of a scaler's destination size (packed, `stride` apart, indexed by slot)
+static int dec_scaled_win(pfv_dec_session *s, pfv_scaler *sc, int first, int count, const uint8_t *filtered, size_t filtered_stride, uint8_t *dst, size_t stride)
+{
+    FrameGeom g;
+    SseOperand src;
+    const int rc = dec_shown_operand(s, first, count, filtered, filtered_stride, &g, &src);
+    if (rc) return rc;
+    return scale_launch(sc, count, src.base, src.padded ? PFV_FRAME_PADDED : PFV_FRAME_PACKED, (size_t)src.stride, dst + (size_t)first * stride, stride);
+}
+// the decode calls' share (dec_step): the window's pictures into the output of pfv_dec_set_output_rgb_dev, its resized frames into the output of
+// pfv_dec_set_output_scaled_dev -- from one operand: a deblocked picture that no planar output takes is filtered once for both
 static int dec_present_step(pfv_dec_session *s)
 {
-    return dec_present_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride, s->rgb_out, s->rgb_format, s->rgb_pitch, s->rgb_stride);
+    FrameGeom g;
+    SseOperand src;
+    int rc = dec_shown_operand(s, s->win_first, s->win_count, s->frames_out, s->out_stride, &g, &src);
+    if (!rc && s->rgb_out) rc = present_launch(s->ctx, g, src, s->rgb_out + (size_t)s->win_first * s->rgb_stride, s->rgb_format, s->rgb_pitch, s->rgb_stride);
+    if (!rc && s->scaled_out)
+        rc = scale_launch(s->scaled_sc, s->win_count, src.base, src.padded ? PFV_FRAME_PADDED : PFV_FRAME_PACKED, (size_t)src.stride,
+                          s->scaled_out + (size_t)s->win_first * s->scaled_stride, s->scaled_stride);
+    return rc;
 }
 
 extern "C" {

@@ -102,6 +102,7 @@ struct pfv_enc_session {
     int8_t *st_mv = nullptr;
     uint8_t *st_has = nullptr;
     uint8_t *ingest_frames = nullptr;        // packed frames of all slots made from RGB pictures (pfv_ingest.hip, pfv_enc_ingest_rgb_dev)
+    uint8_t *scale_frames = nullptr;         // packed frames of all slots resized from frames of another size (pfv_scale.hip, pfv_enc_scale_dev)
     // distortion (pfv_quality.hip): the macroblock map when the caller passes none, the plane sums and where they land on the host
     uint32_t *q_map = nullptr;
     uint64_t *q_sse = nullptr;
@@ -177,12 +178,16 @@ struct pfv_dec_session {
     size_t rgb_pitch = 0, rgb_stride = 0;
     uint8_t *db_scratch = nullptr;           // packed frames of all slots: where a deblocked picture waits for k_present_rgb when no planar output takes it
     uint8_t *st_rgb = nullptr;               // staging of pfv_dec_get_frame_rgb
+    pfv_scaler *scaled_sc = nullptr;         // resized output beside the others (pfv_scale.hip, pfv_dec_set_output_scaled_dev): the caller's scaler,
+    uint8_t *scaled_out = nullptr;           // packed frames of its destination size, scaled_stride apart, by slot
+    size_t scaled_stride = 0;
 };
 static int enc_report_enqueue(pfv_enc_session *s);   // pfv_quality.hip
 static int dec_deblock_win(pfv_dec_session *s, int first, int count, uint8_t *frames_out_dev, size_t out_stride);   // pfv_deblock.hip
 static int enc_ssim_enqueue(pfv_enc_session *s);     // pfv_ssim.hip
 static int dec_present_scratch(pfv_dec_session *s, const char *what);   // pfv_present.hip
 static int dec_present_step(pfv_dec_session *s);
+struct pfv_scaler;                                   // pfv_scale.hip
 
 extern "C" {
 
@@ -261,7 +266,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->scale_frames, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -813,8 +818,8 @@ static int dec_step(pfv_dec_session *s, bool pframe, const int8_t *mv_dev, const
     for (int i = 0; i < 3; i++) s->db_auto[i] = s->db_table[qidx[i]];   // dec_geom has checked the indices; a u8 names one of the first 256 tables
     if (s->frames_out && s->db_mode) rc = dec_deblock_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
     else if (s->frames_out && !fused_output_ok(s)) rc = dec_crop_win(s, s->win_first, s->win_count, s->frames_out, s->out_stride);
-    if (rc || !s->rgb_out) return rc;
-    return dec_present_step(s);   // the window's RGB pictures, from what has just been decoded (and filtered)
+    if (rc || (!s->rgb_out && !s->scaled_out)) return rc;
+    return dec_present_step(s);   // the window's RGB pictures and resized frames, from what has just been decoded (and filtered)
 }
 extern "C" {
 

@@ -97,6 +97,11 @@ struct pfv_encoder {
     bool rgb_on = false;
     int rgb_format = 0, rgb_chroma = 0;    // PFV_PIX_*, PFV_CHROMA_*
     uint8_t *rgb_scratch = nullptr;        // device: where the picture waits for k_ingest_rgb; holds any format; made by the set call
+    size_t rgb_scratch_cap = 0;
+    // resized input (pfv_encoder_set_input_size): the (y, u, v) -- or the picture -- of every call have the size src_w x src_h
+    pfv_scaler *scaler = nullptr;          // src_w x src_h -> width x height; owned
+    int src_w = 0, src_h = 0;
+    uint8_t *scale_src = nullptr;          // device: the packed frame of the source size that waits for k_scale; made by the set call
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -505,7 +510,13 @@ struct pfv_decoder {
     bool rgb_on = false;                   // pfv_decoder_set_output_rgb: the callback gets one tight picture in rgb_format instead of the planes
     int rgb_format = 0;
     PinnedBuf<uint8_t> rgbframe;           // ... in host memory
-    uint8_t *rgb_dev = nullptr;            // ... in device memory (while frame_dev is set)
+    uint8_t *rgb_dev = nullptr;            // ... in device memory (while frame_dev is set, and wherever the picture is made from a resized frame)
+    size_t rgb_dev_cap = 0;
+    // pfv_decoder_set_output_size: the callback gets the frame resized to out_w x out_h (and, with rgb_on, the picture of that frame)
+    pfv_scaler *scaler = nullptr;          // width x height -> out_w x out_h; owned
+    int out_w = 0, out_h = 0;
+    uint8_t *scaled_dev = nullptr;         // one packed out_w x out_h frame in device memory: k_scale's destination
+    PinnedBuf<uint8_t> scaledframe;        // ... and where it lands in host memory
     // look-ahead: ring of events in stream order, [head, head + count)
     std::vector<std::unique_ptr<DecEvent>> ring;
     size_t head = 0, count = 0;
@@ -654,7 +665,7 @@ static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const 
 {
     if (!planes_given(e, y, u, v)) return fail(e->ctx, PFV_ERR_BAD_ARG, e->rgb_on ? "RGB input is on: y is the picture, u and v must be NULL" : "null plane");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
-    if (e->rgb_on && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted planes come back down
+    if ((e->rgb_on || e->scaler) && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted / resized planes come back down
         pfv_ctx *ctx = e->ctx;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         int rc = enc_staging(e->hot);
@@ -700,19 +711,25 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
 {
     pfv_enc_session *s = e->hot;
     pfv_ctx *ctx = e->ctx;
-    const size_t ny = (size_t)e->width * e->height, nc = (size_t)(e->width / 2) * (e->height / 2);
-    if (e->rgb_on) {   // the picture up into the encoder's scratch, one k_ingest_rgb into the staging
-        const size_t row = pfv_rgb_row_bytes(e->width, e->rgb_format);
-        hipError_t he = hipMemcpyAsync(e->rgb_scratch, y, row * (size_t)e->height, hipMemcpyHostToDevice, ctx->stream);
+    // what the caller hands over has the size iw x ih; its planar form goes to `planar`: the staging itself, or where it waits for k_scale
+    const int iw = e->scaler ? e->src_w : e->width, ih = e->scaler ? e->src_h : e->height;
+    const size_t ny = (size_t)iw * ih, nc = (size_t)(iw / 2) * (ih / 2);
+    uint8_t *planar = e->scaler ? e->scale_src : s->st_frames;
+    if (e->rgb_on) {   // the picture up into the encoder's scratch, one k_ingest_rgb
+        const size_t row = pfv_rgb_row_bytes(iw, e->rgb_format);
+        hipError_t he = hipMemcpyAsync(e->rgb_scratch, y, row * (size_t)ih, hipMemcpyHostToDevice, ctx->stream);
         if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "picture upload"); }
-        return ingest_launch(ctx, e->width, e->height, 1, e->rgb_scratch, e->rgb_format, row, row * (size_t)e->height, s->st_frames, ny + 2 * nc, e->rgb_chroma);
+        const int rc = ingest_launch(ctx, iw, ih, 1, e->rgb_scratch, e->rgb_format, row, row * (size_t)ih, planar, ny + 2 * nc, e->rgb_chroma);
+        if (rc) return rc;
+    } else {
+        const bool packed = u == y + ny && v == u + nc;   // a packed frame: one copy
+        hipError_t he = hipMemcpyAsync(planar, y, packed ? ny + 2 * nc : ny, hipMemcpyHostToDevice, ctx->stream);
+        if (!packed && he == hipSuccess) he = hipMemcpyAsync(planar + ny, u, nc, hipMemcpyHostToDevice, ctx->stream);
+        if (!packed && he == hipSuccess) he = hipMemcpyAsync(planar + ny + nc, v, nc, hipMemcpyHostToDevice, ctx->stream);
+        if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "plane upload"); }
     }
-    const bool packed = u == y + ny && v == u + nc;   // a packed frame: one copy
-    hipError_t he = hipMemcpyAsync(s->st_frames, y, packed ? ny + 2 * nc : ny, hipMemcpyHostToDevice, ctx->stream);
-    if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny, u, nc, hipMemcpyHostToDevice, ctx->stream);
-    if (!packed && he == hipSuccess) he = hipMemcpyAsync(s->st_frames + ny + nc, v, nc, hipMemcpyHostToDevice, ctx->stream);
-    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "plane upload"); }
-    return PFV_OK;
+    if (!e->scaler) return PFV_OK;
+    return scale_launch(e->scaler, 1, e->scale_src, PFV_FRAME_PACKED, ny + 2 * nc, s->st_frames, (size_t)s->geom.src_frame_bytes);   // one k_scale into the staging
 }
 
 // One frame through the device entropy stage: planes up (unless the i-frame budget's probe has put them there: `staged`), kernels, payload size
@@ -755,6 +772,21 @@ PFV_API int pfv_encoder_set_device_entropy(pfv_encoder *e, int on)
     return PFV_OK;
 }
 
+// the encoder's device scratch for the input switches that are on, at the size of what the caller hands over; made by the set calls only
+static int enc_input_scratch(pfv_encoder *e)
+{
+    pfv_ctx *ctx = e->ctx;
+    const int iw = e->scaler ? e->src_w : e->width, ih = e->scaler ? e->src_h : e->height;
+    if (e->scaler && !e->scale_src) HIP_TRY(ctx, hipMalloc((void **)&e->scale_src, pfv_frame_bytes(iw, ih)));
+    const size_t pic = (size_t)iw * ih * 4;
+    if (e->rgb_on && e->rgb_scratch_cap < pic) {
+        if (e->rgb_scratch) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(e->rgb_scratch); e->rgb_scratch = nullptr; e->rgb_scratch_cap = 0; }
+        HIP_TRY(ctx, hipMalloc((void **)&e->rgb_scratch, pic));
+        e->rgb_scratch_cap = pic;
+    }
+    return PFV_OK;
+}
+
 // RGB picture input: while on, the (y, u, v) of every encode_* / probe_* call is (one tight picture in `format`, NULL, NULL); pack_frame and
 // upload_planes are the two places a frame enters, and the only ones that know (include/pfv_hip_ext.h, "RGB / RGBA picture input")
 PFV_API int pfv_encoder_set_input_rgb(pfv_encoder *e, int on, int format, int chroma)
@@ -770,9 +802,29 @@ PFV_API int pfv_encoder_set_input_rgb(pfv_encoder *e, int on, int format, int ch
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = enc_staging(e->hot);
     if (rc) return rc;
-    if (!e->rgb_scratch) HIP_TRY(ctx, hipMalloc((void **)&e->rgb_scratch, (size_t)e->width * e->height * 4));
     e->rgb_on = true; e->rgb_format = format; e->rgb_chroma = chroma;
-    return PFV_OK;
+    return enc_input_scratch(e);
+}
+
+// Resized input: while on, what every encode_* / probe_* call takes -- the planes, or under pfv_encoder_set_input_rgb the picture -- has the
+// size src_w x src_h; it goes up into scratch of the encoder and one k_scale puts the frame into the session's frame staging (upload_planes)
+PFV_API int pfv_encoder_set_input_size(pfv_encoder *e, int src_w, int src_h, int kind)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    pfv_ctx *ctx = e->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    pfv_scaler *sc = nullptr;
+    if (src_w != 0) {
+        int rc = PFV_OK;
+        if (!(sc = pfv_scaler_create(ctx, src_w, src_h, e->width, e->height, kind, &rc))) return rc;
+        if ((rc = enc_staging(e->hot))) { pfv_scaler_destroy(sc); return rc; }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // nothing reads the old tables or scratch any more
+    pfv_scaler_destroy(e->scaler);
+    if (e->scale_src) { (void)hipFree(e->scale_src); e->scale_src = nullptr; }
+    e->scaler = sc;
+    e->src_w = sc ? src_w : 0; e->src_h = sc ? src_h : 0;
+    return enc_input_scratch(e);
 }
 
 // Frame reports: with them on, every encode_* call also measures the frame it was given against the reconstruction it leaves in prev_frame
@@ -1210,10 +1262,12 @@ PFV_API int pfv_encoder_drain(pfv_encoder *e, const uint8_t **data, size_t *len)
 PFV_API void pfv_encoder_destroy(pfv_encoder *e)
 {
     if (!e) return;
-    if (e->rgb_scratch) {
+    if (e->rgb_scratch || e->scaler) {
         (void)hipSetDevice(e->ctx->device);
         (void)hipStreamSynchronize(e->ctx->stream);
-        (void)hipFree(e->rgb_scratch);
+        if (e->rgb_scratch) (void)hipFree(e->rgb_scratch);
+        if (e->scale_src) (void)hipFree(e->scale_src);
+        pfv_scaler_destroy(e->scaler);
     }
     pfv_enc_session_destroy(e->hot);
     delete e;

@@ -65,7 +65,22 @@ class Decoder:
         from .quality import pix_format, rgb_shape
         m = pix_format(fmt)
         self.ctx.check(self.ctx._lib.pfv_decoder_set_output_rgb(self.handle, 1 if on else 0, m))
-        self._rgb_shape = rgb_shape(self.ctx, self.width(), self.height(), m) if on else None
+        self._rgb_format = m if on else None
+        self._output_shapes()
+
+    def set_output_size(self, width=0, height=0, kind="bicubic"):
+        """``onvideo`` receives the frame -- under set_output_rgb the picture -- resized on the device to width x height with kind "bilinear" /
+        "bicubic" / "lanczos3"; width 0 switches it off; width() / height() keep reporting the stream's size (pfv_decoder_set_output_size)"""
+        from .scale import scale_kind
+        self.ctx.check(self.ctx._lib.pfv_decoder_set_output_size(self.handle, int(width or 0), int(height or 0), scale_kind(kind)))
+        self._out_size = (int(width), int(height)) if width else None
+        self._output_shapes()
+
+    def _output_shapes(self):
+        from .quality import rgb_shape
+        w, h = getattr(self, "_out_size", None) or (self.width(), self.height())
+        m = getattr(self, "_rgb_format", None)
+        self._rgb_shape = rgb_shape(self.ctx, w, h, m) if m is not None else None
 
     def entropy_counts(self) -> dict:
         """packets whose run streams the device read / that its stage left to the host parser (pfv_decoder_entropy_counts)"""
@@ -195,6 +210,9 @@ class GopDecoder(Decoder):
 
     def set_output_rgb(self, on=True, fmt="rgb8"):
         raise NotImplementedError("pfv_gop_decoder has no RGB switch: pass its device frames to pfv_frames_to_rgb_dev")
+
+    def set_output_size(self, width=0, height=0, kind="bicubic"):
+        raise NotImplementedError("pfv_gop_decoder has no resize switch: pass its device frames to pfv_scaler_run_dev")
 
     def _callback(self, onvideo):
         if not self.raw:

@@ -68,7 +68,22 @@ class Encoder:
         from .quality import chroma_mode, pix_format, rgb_shape
         m = pix_format(fmt)
         self.ctx.check(self.ctx._lib.pfv_encoder_set_input_rgb(self.handle, 1 if on else 0, m, chroma_mode(chroma)))
-        self._rgb_shape = rgb_shape(self.ctx, self.width, self.height, m) if on else None
+        self._rgb_format = m if on else None
+        self._input_shapes()
+
+    def set_input_size(self, src_width=0, src_height=0, kind="bicubic"):
+        """the encode_* / probe_* methods take frames -- under set_input_rgb pictures -- of src_width x src_height, resized on the device to the
+        encoder's size with kind "bilinear" / "bicubic" / "lanczos3"; src_width 0 switches it off (pfv_encoder_set_input_size)"""
+        from .scale import scale_kind
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_input_size(self.handle, int(src_width or 0), int(src_height or 0), scale_kind(kind)))
+        self._in_size = (int(src_width), int(src_height)) if src_width else None
+        self._input_shapes()
+
+    def _input_shapes(self):
+        from .quality import rgb_shape
+        w, h = getattr(self, "_in_size", None) or (self.width, self.height)
+        m = getattr(self, "_rgb_format", None)
+        self._rgb_shape = rgb_shape(self.ctx, w, h, m) if m is not None else None
 
     def _input(self, frame):
         """the (y, u, v) of a C call: the frame's planes, or under set_input_rgb (picture, NULL, NULL)"""
@@ -83,7 +98,7 @@ class Encoder:
         if getattr(self, "_rgb_shape", None):
             assert not self.finished
             return
-        assert frame.width == self.width and frame.height == self.height                                  # src/enc.rs:76-79
+        assert (frame.width, frame.height) == (getattr(self, "_in_size", None) or (self.width, self.height))  # src/enc.rs:76-79
         assert frame.plane_y.width == frame.width and frame.plane_y.height == frame.height
         assert frame.plane_u.width == frame.width // 2 and frame.plane_u.height == frame.height // 2
         assert frame.plane_v.width == frame.width // 2 and frame.plane_v.height == frame.height // 2
@@ -402,6 +417,9 @@ class GopEncoder(Encoder):
 
     def set_input_rgb(self, on=True, fmt="rgb8", chroma="point"):
         raise NotImplementedError("pfv_gop_encoder has no RGB switch: convert with pfv_frames_from_rgb_dev and use its _dev forms")
+
+    def set_input_size(self, src_width=0, src_height=0, kind="bicubic"):
+        raise NotImplementedError("pfv_gop_encoder has no resize switch: resize with pfv_scaler_run_dev and use its _dev forms")
 
     def encode_iframe(self, frame):
         self.ctx.check(self.ctx._lib.pfv_gop_encoder_encode_iframe(self.handle, *self._planes(frame)))

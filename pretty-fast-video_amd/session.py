@@ -214,6 +214,14 @@ class EncoderSession(_Geometry):
                                                             chroma_mode(chroma), ctypes.byref(out)))
         return int(out.value)
 
+    def scale_dev(self, scaler, frames_dev: int, src_stride: int = 0) -> int:
+        """asynchronous: the frames of the scaler's source size of the window's slots (slot k's at frames_dev + k * src_stride; 0: packed)
+        resized into slot k's frame of a packed buffer the session owns; returns that buffer's device address, a `frames_dev` for the
+        encode, probe, distortion_dev and ssim_dev calls (pfv_enc_scale_dev)"""
+        out = ctypes.c_void_p()
+        self.ctx.check(self.ctx._lib.pfv_enc_scale_dev(self.handle, scaler.handle, ctypes.c_void_p(frames_dev), int(src_stride), ctypes.byref(out)))
+        return int(out.value)
+
     # GOP-batched use: the slots hold the GOPs of one stream (include/pfv_hip.h, pfv_enc_session_set_window) -----------
     def set_frame_stride(self, stride_bytes: int = 0):
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_frame_stride(self.handle, int(stride_bytes)))
@@ -459,6 +467,14 @@ class DecoderSession(_Geometry):
         """asynchronous; rows `pitch` bytes apart (0: tight), pictures `stride` apart (0: pitch x height) (pfv_dec_get_frame_rgb_dev)"""
         from .quality import pix_format
         self.ctx.check(self.ctx._lib.pfv_dec_get_frame_rgb_dev(self.handle, ctypes.c_void_p(dst_dev), pix_format(fmt), int(pitch), int(stride)))
+
+    def set_output_scaled_dev(self, scaler, dst_dev, stride: int = 0):
+        """a resized output beside the others: every decode call also writes the frames of its window's slots at the scaler's destination
+        size, packed, `stride` apart (0: the frame size), indexed by slot; dst_dev None switches it off.  The scaler must stay open while
+        it is set (pfv_dec_set_output_scaled_dev)"""
+        self._scaled_keep = scaler if dst_dev else None
+        self.ctx.check(self.ctx._lib.pfv_dec_set_output_scaled_dev(self.handle, scaler.handle if (scaler is not None and dst_dev) else None,
+                                                                  ctypes.c_void_p(dst_dev or 0), int(stride)))
 
     def set_output_rgb_dev(self, dst_dev, fmt="rgb8", pitch: int = 0, stride: int = 0):
         """an RGB output beside the planar ones: every decode call also writes the pictures of its window's slots, indexed by slot

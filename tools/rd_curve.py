@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -73,6 +73,10 @@ their timing at 96 x 1080p, ladders 0,2,5,7,10 and 0..10, by the methods above: 
 k_probe_pframe_ssim, k_probe_ssim_windows, the RD probe's tail); B = per rung the trial encode to the size + pfv_enc_distortion_dev +
 pfv_enc_ssim_dev; C = the RD probe of the same frame type (what the SSIM half adds is A - C).  Sizes, plane sums and SSIM sums against the
 trial encodes at every rung of all streams; the bytes of the block-sum map.
+--time-scale (on the GPU box) adds thirteen lines: k_scale on 96 x 1080p frames in HBM -> 720p, -> 540p, -> 240x136 and 540p -> 1080p, each for
+the three kinds, against the bytes it must move (source read once plus destination written once), and pfv_dec_get_frame_dev (k_crop_frames) on
+the same frames as the streaming yardstick; "rate_over_crop_rate" is the fraction of its byte rate.  Method and the PFV_HIP_LIB rule as
+--time-present (with PFV_HIP_LIB: one WIDTH x HEIGHT stream, the rows only).
 """
 import argparse
 import ctypes
@@ -344,6 +348,71 @@ def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=
             "a_present_ms": med["a_present"], "b_crop_plus_per_stream_ms": med["b_crop_plus_per_stream"], "c_crop_ms": med["c_crop"],
             "bytes": moved, "GBps": gbps, "a_over_b_time": over(med["a_present"], med["b_crop_plus_per_stream"]),
             "a_rate_over_c_rate": over(gbps["a_present"], gbps["c_crop"]) if gbps["a_present"] else None, "rounds_ms": res}
+
+
+def scale_cases(w, h):
+    """the four size pairs of --time-scale for a w x h frame: down to 2/3, 1/2 and 1/8 (sizes rounded up to even), and w/2 x h/2 up to w x h"""
+    ev = lambda n, num, den: ((n * num + den - 1) // den + 1) // 2 * 2      # noqa: E731
+    return [(w, h, ev(w, 2, 3), ev(h, 2, 3)), (w, h, ev(w, 1, 2), ev(h, 1, 2)), (w, h, ev(w, 1, 8), ev(h, 1, 8)), (ev(w, 1, 2), ev(h, 1, 2), w, h)]
+
+
+def time_scale(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
+    """k_scale (pfv_scaler_run_dev, packed frames in HBM) per size pair and kind, and pfv_dec_get_frame_dev (k_crop_frames) of n_streams w x h
+    frames as the streaming yardstick: medians of HIP-event times after warm-up, the ways alternated per round"""
+    lib = ctx._lib
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    f0, planar, coef = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams), ctx.alloc(n_streams * tb * 512)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, f0)
+    enc = pkg.EncoderSession(ctx, w, h, 5, n_streams)
+    dec = pkg.DecoderSession(ctx, w, h, np.stack(pkg.qtables_from_quality(5)[:4]), n_streams)
+    enc.encode_iframe_dev(f0, coef)
+    dec.decode_iframe_dev(coef)
+    enc.close()
+    ctx.free(coef)
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got)
+    ways, moved, scalers, dsts = {"crop": lambda: dec.get_frame_dev(planar)}, {"crop": n_streams * (fb + int(lib.pfv_padded_frame_bytes(w, h)))}, [], {}
+    for sw, sh, dw, dh in scale_cases(w, h):
+        sfb, dfb = int(lib.pfv_frame_bytes(sw, sh)), int(lib.pfv_frame_bytes(dw, dh))
+        if (dw, dh) not in dsts:
+            dsts[(dw, dh)] = ctx.alloc(dfb * n_streams) if (dw, dh) != (w, h) else planar
+        for kind in ("bilinear", "bicubic", "lanczos3"):
+            sc = pkg.Scaler(ctx, sw, sh, dw, dh, kind)
+            scalers.append(sc)
+            key = f"{sw}x{sh}->{dw}x{dh} {kind}"
+            ways[key] = (lambda sc=sc, dst=dsts[(dw, dh)]: sc.run_dev(n_streams, f0, dst))      # the first sw x sh bytes of f0's frames serve as the smaller source too
+            moved[key] = n_streams * (sfb + dfb)
+    res = {k: [] for k in ways}
+    for _ in range(rounds):
+        for key, fn in ways.items():
+            res[key].append(median_ms(fn))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    for sc in scalers:
+        sc.close()
+    dec.close()
+    for p in [f0, planar] + [d for d in dsts.values() if d != planar]:
+        ctx.free(p)
+    over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
+    med = {k: statistics.median(v) for k, v in res.items()}
+    gbps = {k: over(moved[k], med[k] * 1e6) for k in ways}
+    rows = []
+    for key in ways:
+        rows.append({"shape": f"{n_streams} x {w}x{h}", "case": key, "ms": med[key], "bytes": moved[key], "GBps": gbps[key],
+                     "rate_over_crop_rate": over(gbps[key], gbps["crop"]) if gbps[key] else None, "rounds_ms": res[key], "samples_per_round": samples})
+    return rows
 
 
 def time_ingest(pkg, ctx, fmt, chroma, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
@@ -1033,6 +1102,7 @@ def main():
     ap.add_argument("--time-deblock", action="store_true")
     ap.add_argument("--time-present", action="store_true")
     ap.add_argument("--time-ingest", action="store_true")
+    ap.add_argument("--time-scale", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -1059,6 +1129,10 @@ def main():
                     for chroma in ("point", "box"):
                         kw = dict(warmup=1, samples=2, rounds=1) if emu else {}
                         print(json.dumps({"time_ingest": time_ingest(pkg, ctx, fmt, chroma, **shape, **kw)}), flush=True)
+        if a.time_scale:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the rows only
+            for row in (time_scale(pkg, ctx, 1, a.width, a.height, warmup=1, samples=2, rounds=1) if emu else time_scale(pkg, ctx)):
+                print(json.dumps({"time_scale": row}), flush=True)
         if a.time_kernel:
             print(json.dumps({"time_kernel": time_kernels(pkg, ctx)}), flush=True)
         if a.probe:
