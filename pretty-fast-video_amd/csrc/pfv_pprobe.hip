@@ -25,38 +25,21 @@ static int pprobe_acc(pfv_enc_session *s)
     return PFV_OK;
 }
 
-// slots [win_first, win_first + win_count): the same launches on shifted bases (see enc_launch); geometry and grid are k_enc_pframe's
 static int pprobe_launch(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev)
 {
     pfv_ctx *ctx = s->ctx;
     int rc = pprobe_acc(s);
     if (rc) return rc;
-    const size_t first = (size_t)s->win_first, R = (size_t)s->n_rungs;
-    const size_t stride = s->in_stride ? s->in_stride : (size_t)s->geom.src_frame_bytes;
-    const uint8_t *src = frames_dev + first * stride;
-    const FrameGeom g = enc_win_geom(s, s->win_count, src);
-    const uint8_t *ref = s->prev[s->cur] + first * (size_t)s->geom.pad_frame_bytes;
-    uint32_t *acc = s->pprobe_acc + first * R * kPProbeAcc;
-    const float *min_err = reinterpret_cast<const float *>(s->pprobe_acc + (size_t)s->n_streams * R * kPProbeAcc);
-    if (s->flt) hipLaunchKernelGGL(k_probe_pframe<true>, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, src, ref, (const QTab *)s->qtab_dev, s->n_rungs, min_err, -2, acc);
-    else hipLaunchKernelGGL(k_probe_pframe<false>, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, src, ref, (const QTab *)s->qtab_dev, s->n_rungs, min_err, -2, acc);
-    hipLaunchKernelGGL(k_pprobe_sizes, dim3((unsigned)((size_t)s->win_count * R)), dim3(64), 0, ctx->stream, acc, sizes_dev + first * R,
-                       stats_dev ? stats_dev + first * R * kPProbeStats : (uint32_t *)nullptr);
+    const ProbeWin w = probe_win(s, frames_dev, true);
+    const QTab *qt = (const QTab *)s->qtab_dev;
+    uint32_t *acc = s->pprobe_acc + w.first * w.R * kPProbeAcc;
+    if (s->flt) hipLaunchKernelGGL(k_probe_pframe<true>, dim3(penc_blocks(ctx, w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, w.ref, qt, s->n_rungs, w.min_err, -2, acc);
+    else hipLaunchKernelGGL(k_probe_pframe<false>, dim3(penc_blocks(ctx, w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, w.ref, qt, s->n_rungs, w.min_err, -2, acc);
+    hipLaunchKernelGGL(k_pprobe_sizes, dim3((unsigned)((size_t)s->win_count * w.R)), dim3(64), 0, ctx->stream, acc, sizes_dev + w.first * w.R,
+                       stats_dev ? stats_dev + w.first * w.R * kPProbeStats : (uint32_t *)nullptr);
     return launch_check(ctx, "k_probe_pframe / k_pprobe_sizes");
 }
 
-extern "C" {
-
-PFV_API int pfv_enc_probe_pframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev)
-{
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames_dev || !sizes_dev) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_pframe_dev: null buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return pprobe_launch(s, frames_dev, sizes_dev, stats_dev);
-}
-
-}  // extern "C"
 // the frames in the session's staging (all slots, packed) -> sizes_out [n_streams][n_rungs] and, where asked for, stats_out
 // [n_streams][n_rungs][kPProbeStats]; synchronises
 static int pprobe_staged(pfv_enc_session *s, uint32_t *sizes_out, uint32_t *stats_out = nullptr)
@@ -71,20 +54,18 @@ static int pprobe_staged(pfv_enc_session *s, uint32_t *sizes_out, uint32_t *stat
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
 }
+
 extern "C" {
 
+PFV_API int pfv_enc_probe_pframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev)
+{
+    int rc = probe_dev_enter(s, frames_dev && sizes_dev, "pfv_enc_probe_pframe_dev");
+    return rc ? rc : pprobe_launch(s, frames_dev, sizes_dev, stats_dev);
+}
 PFV_API int pfv_enc_probe_pframe(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out)
 {
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames || !sizes_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_pframe: null buffer");
-    if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_pframe: the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
-    if (ctx->capturing) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_pframe: host-pointer entry points cannot be recorded");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = enc_staging(s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams, hipMemcpyHostToDevice, ctx->stream));
-    return pprobe_staged(s, sizes_out);
+    int rc = probe_host_enter(s, frames, sizes_out != nullptr, "pfv_enc_probe_pframe");
+    return rc ? rc : pprobe_staged(s, sizes_out);
 }
 
 }  // extern "C"

@@ -6,10 +6,13 @@
 // normalised histogram (rle.rs:49-66, src/huffman.rs:71-119) and sumsize the sum of coeff_size over the non-zero values.  The source read, the
 // pixel bias, both 1-D transforms and the DCT_SCALE_FACTOR multiply (quant_scale) do not depend on the rung; only trunc(n * rcp) does.
 //
-//   k_probe_iframe  strip mapping and geometry of k_enc_iframe (one wavefront = a strip of 8 macroblocks, or half of one under the 16-lane
-//                   mapping).  Per half-macroblock: unpack, (px - 128) << 8, rows, transpose, columns, quant_scale -- the scaled coefficients
-//                   of the lane's subblocks stay in registers (as floats: |n| <= 5160).  Then per rung r, with the reciprocals of all rungs
-//                   staged in LDS once:
+//   probe_forward_row   one half-macroblock: unpack, (px - 128) << 8 (or the halved residual), rows, transpose, columns, quant_scale.  The
+//                   forward half of the closed loop, once for all six probe kernels and both arithmetics.
+//   probe_strip_front   the front end of the three i-frame kernels behind their strip mapping (k_enc_iframe's: one wavefront = a strip of 8
+//                   macroblocks, or half of one under the 16-lane mapping; the two early-outs stay in the kernels): source rows, scaled
+//                   coefficients, zigzag positions.
+//   k_probe_iframe  the mapping and the front end -- the scaled coefficients of the lane's subblocks stay in registers (as floats: |n| <= 5160).  Then per
+//                   rung r, with the reciprocals of all rungs staged in LDS once per wavefront:
 //                     per value   q = trunc(n * rcp) (quant_div); e = q's exponent field: q != 0 <=> e != 0, coeff_size = bit length + 1 =
 //                                 e - 125.  One bit into the lane's part of the subblock's 64-bit non-zero map at the value's zigzag position,
 //                                 one count into a 64-bit word of sixteen 4-bit fields (a lane holds 8 values of a subblock), max(e) for the
@@ -23,7 +26,7 @@
 //                     per wavefront  the lanes' counts -- sixteen 8-bit fields, sizes and runs together; sumsize = four v_dot4 over the size
 //                                 fields -- are widened to 16-bit fields, summed over each 16-lane row with DPP and over the four rows on the
 //                                 scalar side, and seventeen lanes add them to acc[stream][rung] with one vector atomic.
-//   probe_rung_loop the "per rung" part above as a device function: k_probe_pframe (pfv_pprobe_kernels.hip) runs it on residuals.
+//   probe_rung_loop the "per rung" part above as a device function: the p-frame probes (pfv_pprobe_kernels.hip) run it on residuals.
 //   k_probe_sizes   one wavefront per (stream, rung): ent_build_codes_wave on the 16 counts, the size, and the accumulator cleared for the next
 //                   call -- so a call needs no host-side clear and no host synchronisation, and a recorded pair of launches can be replayed.
 // Included by pfv_capi.hip behind pfv_entropy_kernels.hip.
@@ -209,6 +212,81 @@ __device__ __forceinline__ void probe_rung_loop(const f2 (&nn)[LPM == 8 ? 2 : 1]
     }
 }
 
+// The forward half of the closed loop for one half-macroblock, rd_recon_row's mirror image (pfv_rdprobe_kernels.hip): row = the lane's 16 source
+// pixels -> nn = (m * SCALE) >> 16 of its two subblocks in column layout, nn[k] = rows k of subblocks 2h and 2h + 1, column i.  An i-frame:
+// (px - 128) << 8 (src/common.rs:291); RESIDUAL: calc_residuals against the prediction's row `pred` (:118-119), delta / 2 truncating, << 8
+// (:304).  Rows, transpose through the macroblock's exchange region `mb`, columns, quant_scale: forward_half's / penc_half's arithmetic, FLT in f32.
+template <bool FLT, bool RESIDUAL = false>
+__device__ __forceinline__ void probe_forward_row(const uint4 &row, const uint4 &pred, int *mb, int i, int quarter, const LaneQ lq, f2 (&nn)[8])
+{
+    if (FLT) {
+        f2 x[8], pp[8];
+        unpack_row_f(row, x);
+        if (RESIDUAL) unpack_row_f(pred, pp);
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = RESIDUAL ? residual_f(x[k], pp[k]) : x[k] * f2s(256.0f) - f2s(32768.0f);
+        ffdct8(x);
+        f_rows_to_cols(x, mb, i, quarter);
+        ffdct8(x);
+#pragma unroll
+        for (int k = 0; k < 8; k++) nn[k] = quant_scale(x[k], lq.scale(k));
+    } else {
+        int v[2][8], pp[2][8];
+        unpack_row(row, v);
+        if (RESIDUAL) unpack_row(pred, pp);
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[s][k] = (int)((unsigned)(RESIDUAL ? tdiv2(v[s][k] - pp[s][k]) : v[s][k] - 128) << 8);
+        }
+        fdct8(v[0]);
+        fdct8(v[1]);
+        rows_to_cols2(v, mb, i, quarter);
+        fdct8(v[0]);
+        fdct8(v[1]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int scale = lq.scale(k);
+            nn[k] = f2{(float)(wmul24(v[0][k], scale) >> 16), (float)(wmul24(v[1][k], scale) >> 16)};
+        }
+    }
+}
+
+// the picture row of the lane's source row `pass` (its column is sp.x0 + m * 16)
+template <int LPM>
+__device__ __forceinline__ int probe_strip_y(const StripPos &sp, int lane, int pass)
+{
+    return sp.y0 + (lane & 7) + 8 * (LPM == 8 ? pass : ((lane >> 3) & 1));
+}
+// The strip probes' front end (k_probe_iframe, _rd, _ssim), behind the kernel's two early-outs: everything that does not depend on the rung.
+// The early-outs stay in the kernels: reported through a helper, StripPos reaches this code through a phi and x0 loses its known-zero low bits
+// (profiles/probe_front_refactor.md).  qtab = the wavefront's table entry, filled by the kernel (fill_qtable: scale and zigzag position; its
+// reciprocal and dequantiser are rung 0's and are not used) like whatever else it stages per wavefront -- the wave_lds_sync in here publishes
+// both.  xw = the wavefront's exchange region -> rows = the lane's source rows, nn = their scaled coefficients (probe_forward_row), zz = the
+// zigzag positions of the lane's values.
+// The order of the rung loops behind a front end is a register matter.  The source rows (and a p-frame's patch rows) end in the distortion
+// loop; kept alive across probe_rung_loop they cost k_probe_pframe_rd (281 registers against 256) and the 8-lane k_probe_iframe_ssim (258) their
+// second wavefront per SIMD.  So those two and k_probe_pframe_ssim run the distortion loop first, and the p-frame forms its picture masks
+// behind the search; k_probe_iframe_rd fits either way and keeps the size loop first (profiles/pframe_rd_probe.md).
+template <bool FLT, int LPM>
+__device__ __forceinline__ void probe_strip_front(const FrameGeom &g, const uint8_t *src, const StripPos &sp, int m, int lane, const int *qtab, int *xw,
+                                                  uint4 (&rows)[LPM == 8 ? 2 : 1], f2 (&nn)[LPM == 8 ? 2 : 1][8], int (&zz)[8])
+{
+    constexpr int kPasses = LPM == 8 ? 2 : 1;
+    const PlaneGeom &p = g.p[sp.plane];
+    const int slot = lane >> 3, i = lane & 7;
+    const uint8_t *plane = frame_src(g, src, sp.stream) + p.src_off;
+#pragma unroll
+    for (int pass = 0; pass < kPasses; pass++) rows[pass] = load_src16(plane, p, sp.x0 + m * 16, probe_strip_y<LPM>(sp, lane, pass));
+    wave_lds_sync();
+    const LaneQ lq{qtab, i};
+    int *mb = xw + slot * kMBPitch;
+#pragma unroll
+    for (int pass = 0; pass < kPasses; pass++) probe_forward_row<FLT>(rows[pass], uint4(), mb, i, slot & 3, lq, nn[pass]);
+#pragma unroll
+    for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
+}
+
 template <bool FLT, int LPM = 8>
 __global__ __launch_bounds__(kThreads) void k_probe_iframe(FrameGeom g, const uint8_t *__restrict__ src, const QTab *__restrict__ qtabs, int n_rungs,
                                                             uint32_t *__restrict__ acc)
@@ -216,67 +294,21 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe(FrameGeom g, const ui
     __shared__ __attribute__((aligned(16))) int xchg[kStripsPerWG][kXchgDwords];
     __shared__ __attribute__((aligned(16))) int qtab_lds[kStripsPerWG][kQTabDwords];
     __shared__ float rcp_lds[kStripsPerWG][kProbeMaxRungs][64];
-    constexpr int kPasses = LPM == 8 ? 2 : 1;
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int gw = xcd_remap((int)blockIdx.x, (int)gridDim.x) * kStripsPerWG + wave;
     const int gstrip = LPM == 8 ? gw : gw >> 1, half_strip = LPM == 8 ? 0 : gw & 1;
-    if (gstrip >= g.strips_per_frame * g.n_streams) return;   // no cross-wavefront sync in this kernel
+    if (gstrip >= g.strips_per_frame * g.n_streams) return;   // no cross-wavefront sync from here on
     const StripPos sp = locate_strip(g, gstrip);
     if (half_strip * 4 >= sp.n_mb) return;
-    const PlaneGeom &p = g.p[sp.plane];
-    const int slot = lane >> 3, i = lane & 7;
-    const int m = LPM == 8 ? slot : half_strip * 4 + (slot >> 1);   // macroblock within the strip
-    int *xw = xchg[wave];
-
-    // scale and zigzag position do not depend on the rung (the entry's reciprocal is rung 0's and is not used); the reciprocals of all rungs
-    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + p.qsel, lane);
-    for (int r = 0; r < n_rungs; r++) rcp_lds[wave][r][lane] = qtabs[4 * r + p.qsel].rcp[lane];   // intra_l / intra_c of rung r
-    const uint8_t *plane = frame_src(g, src, sp.stream) + p.src_off;
-    uint4 rows[kPasses];
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) rows[pass] = load_src16(plane, p, sp.x0 + m * 16, sp.y0 + i + 8 * (LPM == 8 ? pass : (slot & 1)));
-    wave_lds_sync();
-    const LaneQ lq{qtab_lds[wave], i};
-
-    // n = (m * SCALE) >> 16 of the lane's subblocks, column layout: nn[pass][k] = rows k of subblocks 2h and 2h + 1, column i
-    f2 nn[kPasses][8];
-    int *mb = xw + slot * kMBPitch;
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) {
-        if (FLT) {
-            f2 x[8];
-            unpack_row_f(rows[pass], x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) x[k] = x[k] * f2s(256.0f) - f2s(32768.0f);   // (px - 128) << 8, src/common.rs:291
-            ffdct8(x);
-            f_rows_to_cols(x, mb, i, slot & 3);
-            ffdct8(x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) nn[pass][k] = quant_scale(x[k], lq.scale(k));
-        } else {   // forward_half's arithmetic
-            int v[2][8];
-            unpack_row(rows[pass], v);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[s][k] = (int)((unsigned)(v[s][k] - 128) << 8);
-            }
-            fdct8(v[0]);
-            fdct8(v[1]);
-            rows_to_cols2(v, mb, i, slot & 3);
-            fdct8(v[0]);
-            fdct8(v[1]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int scale = lq.scale(k);
-                nn[pass][k] = f2{(float)(wmul24(v[0][k], scale) >> 16), (float)(wmul24(v[1][k], scale) >> 16)};
-            }
-        }
-    }
+    const int m = LPM == 8 ? lane >> 3 : half_strip * 4 + (lane >> 4);   // macroblock within the strip
+    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + g.p[sp.plane].qsel, lane);
+    // the reciprocals of all rungs, per wavefront and for its plane: intra_l / intra_c of rung r
+    for (int r = 0; r < n_rungs; r++) rcp_lds[wave][r][lane] = qtabs[4 * r + g.p[sp.plane].qsel].rcp[lane];
+    uint4 rows[LPM == 8 ? 2 : 1];
+    f2 nn[LPM == 8 ? 2 : 1][8];
     int zz[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
+    probe_strip_front<FLT, LPM>(g, src, sp, m, lane, qtab_lds[wave], xchg[wave], rows, nn, zz);
     const bool present = m < sp.n_mb;   // macroblocks beyond the strip's end count nothing
     probe_rung_loop<LPM, kProbeAcc, kProbeStats>(nn, zz, &rcp_lds[wave][0][0], n_rungs, lane, acc + (size_t)sp.stream * n_rungs * kProbeAcc,
                                                  [&](int) { return present; });

@@ -29,74 +29,51 @@ static int rd_probe_acc(pfv_enc_session *s)
     return rc;
 }
 
-// slots [win_first, win_first + win_count), as probe_launch
 static int rd_probe_launch(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev)
 {
     pfv_ctx *ctx = s->ctx;
     int rc = rd_probe_acc(s);
     if (rc) return rc;
-    const size_t first = (size_t)s->win_first, R = (size_t)s->n_rungs;
-    const size_t stride = s->in_stride ? s->in_stride : (size_t)s->geom.src_frame_bytes;
-    const uint8_t *src = frames_dev + first * stride;
-    const FrameGeom g = enc_win_geom(s, s->win_count, src);
-    uint32_t *acc = s->probe_acc + first * R * kProbeAcc;
-    unsigned long long *sse_acc = (unsigned long long *)s->rd_acc + first * R * 3;
+    const ProbeWin w = probe_win(s, frames_dev, false);
     const QTab *qt = (const QTab *)s->qtab_dev;
-    if (use_small_grid(s->lane_mapping, g)) {
-        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
-        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+    uint32_t *acc = s->probe_acc + w.first * w.R * kProbeAcc;
+    unsigned long long *sse_acc = (unsigned long long *)s->rd_acc + w.first * w.R * 3;
+    if (use_small_grid(s->lane_mapping, w.g)) {
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 16>), dim3(half_strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc);
+        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 16>), dim3(half_strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc);
     } else {
-        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
-        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc);
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_rd<true, 8>), dim3(strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc);
+        else hipLaunchKernelGGL((k_probe_iframe_rd<false, 8>), dim3(strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc);
     }
-    hipLaunchKernelGGL(k_probe_rd_sizes, dim3((unsigned)((size_t)s->win_count * R)), dim3(64), 0, ctx->stream, acc, sizes_dev + first * R,
-                       stats_dev ? stats_dev + first * R * kProbeStats : (uint32_t *)nullptr, sse_acc, (unsigned long long *)sse_dev + first * R * 3);
+    hipLaunchKernelGGL(k_probe_rd_sizes, dim3((unsigned)((size_t)s->win_count * w.R)), dim3(64), 0, ctx->stream, acc, sizes_dev + w.first * w.R,
+                       stats_dev ? stats_dev + w.first * w.R * kProbeStats : (uint32_t *)nullptr, sse_acc, (unsigned long long *)sse_dev + w.first * w.R * 3);
     return launch_check(ctx, "k_probe_iframe_rd / k_probe_rd_sizes");
+}
+
+// the frames in the session's staging (all slots, packed) -> sizes_out [n_streams][n_rungs], sse_out [n_streams][n_rungs][3]: 28 bytes per
+// (stream, rung) through probe_download
+static int rd_probe_staged(pfv_enc_session *s, uint32_t *sizes_out, uint64_t *sse_out)
+{
+    pfv_ctx *ctx = s->ctx;
+    const size_t n = (size_t)s->n_streams * (size_t)s->n_rungs;
+    const size_t sse_bytes = n * 3 * sizeof(uint64_t), size_bytes = n * sizeof(uint32_t);
+    if (!s->rd_out) HIP_TRY(ctx, hipMalloc((void **)&s->rd_out, sse_bytes + size_bytes));
+    int rc = rd_probe_launch(s, s->st_frames, (uint32_t *)((uint8_t *)s->rd_out + sse_bytes), s->rd_out, nullptr);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    return probe_download(ctx, s->rd_out, n, sse_out, nullptr, sizes_out, nullptr);
 }
 
 extern "C" {
 
 PFV_API int pfv_enc_probe_iframe_rd_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev)
 {
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames_dev || !sizes_dev || !sse_dev) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_iframe_rd_dev: null buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return rd_probe_launch(s, frames_dev, sizes_dev, sse_dev, stats_dev);
+    int rc = probe_dev_enter(s, frames_dev && sizes_dev && sse_dev, "pfv_enc_probe_iframe_rd_dev");
+    return rc ? rc : rd_probe_launch(s, frames_dev, sizes_dev, sse_dev, stats_dev);
 }
-
-}  // extern "C"
-// the frames in the session's staging (all slots, packed) -> sizes_out [n_streams][n_rungs], sse_out [n_streams][n_rungs][3]; one download
-// of 28 bytes per (stream, rung) -- the sums first, so that both parts stay aligned -- and one synchronisation
-static int rd_probe_staged(pfv_enc_session *s, uint32_t *sizes_out, uint64_t *sse_out)
-{
-    pfv_ctx *ctx = s->ctx;
-    const size_t n = (size_t)s->n_streams * (size_t)s->n_rungs;
-    const size_t sse_bytes = n * 3 * sizeof(uint64_t), bytes = sse_bytes + n * sizeof(uint32_t);
-    if (!s->rd_out) HIP_TRY(ctx, hipMalloc((void **)&s->rd_out, bytes));
-    std::vector<uint8_t> host(bytes);
-    int rc = rd_probe_launch(s, s->st_frames, (uint32_t *)((uint8_t *)s->rd_out + sse_bytes), s->rd_out, nullptr);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(host.data(), s->rd_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(sse_out, host.data(), sse_bytes);
-    memcpy(sizes_out, host.data() + sse_bytes, n * sizeof(uint32_t));
-    return PFV_OK;
-}
-extern "C" {
-
 PFV_API int pfv_enc_probe_iframe_rd(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out)
 {
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames || !sizes_out || !sse_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_probe_iframe_rd: null buffer");
-    if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd: the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
-    if (ctx->capturing) return fail(ctx, PFV_ERR_STATE, "pfv_enc_probe_iframe_rd: host-pointer entry points cannot be recorded");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = enc_staging(s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams, hipMemcpyHostToDevice, ctx->stream));
-    return rd_probe_staged(s, sizes_out, sse_out);
+    int rc = probe_host_enter(s, frames, sizes_out && sse_out, "pfv_enc_probe_iframe_rd");
+    return rc ? rc : rd_probe_staged(s, sizes_out, sse_out);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // (pfv_probe_kernels.hip) already holds everything that does not depend on the rung -- the source rows and the scaled coefficients nn -- in
 // registers, and what a rung adds for distortion is the closed loop's second half.
 //
-//   k_probe_iframe_rd  k_probe_iframe's strip mapping and front end up to nn, then two rung loops over the same registers:
+//   k_probe_iframe_rd  probe_strip_front (pfv_probe_kernels.hip), then two rung loops over the same registers:
 //                        probe_rung_loop   sizes and counts, the size probe's own (into the same accumulator rows);
 //                        rd_rung_loop      per rung: q = trunc(n * rcp); q * SCALE[z] q[z] with rung r's table (QTab::deq: indexed by zigzag
 //                                          position, as decode does); inverse columns, transpose through the wavefront's exchange region,
@@ -14,14 +14,14 @@
 //                                          k_enc_iframe with the rung's constants; then sum (a - b)^2 = sum a^2 - 2 sum ab + sum b^2 against
 //                                          the lane's source row with v_dot4_u32_u8, bytes at x >= w or y >= h masked out of both operands
 //                                          (what pfv_frames_sse_dev counts).  mb_sum over the macroblock's lanes, a sum over the wavefront
-//                                          (a strip lies in one plane of one stream; 64 lanes x 32 pixels x 255^2 < 2^27), ONE 64-bit vector
-//                                          atomic per wavefront and rung into sse_acc[stream][rung][plane].
-//                      The reciprocals and dequantiser products of all rungs are staged ONCE PER WORKGROUP, for both table sets an i-frame
+//                                          (a strip lies in one plane of one stream; 64 lanes x 32 pixels x 255^2 < 2^27), rd_sse_out: ONE
+//                                          64-bit vector atomic per wavefront and rung into sse_acc[stream][rung][plane].
+//   rd_stage_intra_tables  the reciprocals and dequantiser products of all rungs, staged ONCE PER WORKGROUP for both table sets an i-frame
 //                      uses (luma, chroma: 2 x 11 x 64 x 2 dwords = 11 KiB, one barrier), instead of once per wavefront for the wavefront's
 //                      plane (4 x 11 x 64 x 2 dwords = 22 KiB): 31 KiB of LDS per workgroup instead of 42.
-//   k_probe_rd_sizes   k_probe_sizes's row body (sizes, counts, the rows cleared) and, in the same wavefront, the three plane sums of its
-//                      (stream, rung) moved to the caller's buffer and cleared -- so the pair of launches needs no host-side clear and no
-//                      synchronisation, and can be replayed from a graph.
+//   k_probe_rd_sizes   k_probe_sizes's row body (sizes, counts, the rows cleared) and, in the same wavefront, rd_sums_out: the three plane
+//                      sums of its (stream, rung) moved to the caller's buffer and cleared -- so the pair of launches needs no host-side
+//                      clear and no synchronisation, and can be replayed from a graph.
 // Included by pfv_capi.hip behind pfv_probe_kernels.hip.
 #pragma once
 
@@ -95,9 +95,21 @@ __device__ __forceinline__ uint4 rd_recon_row(const f2 (&nn)[8], const float *rc
     return pack_row(v);
 }
 
-// The distortion half of the rung loop (k_probe_iframe_rd; k_probe_pframe_rd has its own, on residuals and with a skip test per rung): a = the lane's source rows with the
-// pixels outside the picture zeroed, mask = those pixels' byte masks, rcp / deq = the constants of all rungs [n_rungs][64] (LDS), sums = the
-// 64-bit sum of the wavefront's (stream, plane) at rung 0, PITCH words per rung.
+__device__ __forceinline__ uint4 and4(const uint4 &x, const uint4 &m) { return make_uint4(x.x & m.x, x.y & m.y, x.z & m.z, x.w & m.w); }
+
+// the wavefront's sum of the lanes' squared errors into the plane sum of one rung: ONE 64-bit vector atomic
+__device__ __forceinline__ void rd_sse_out(uint32_t lane_sse, int lane, unsigned long long *sum)
+{
+    const int mine = mb_sum((int)lane_sse);   // a lane: < 32 x 255^2; a macroblock: < 2^24; the wavefront: < 2^27
+    uint32_t total = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) total += (uint32_t)__builtin_amdgcn_readlane(mine, 8 * j);
+    if (lane == 0 && total) atomicAdd(sum, (unsigned long long)total);
+}
+
+// The distortion half of the rung loop (k_probe_iframe_rd; the p-frame probes have their own, on residuals and with a skip test per rung): a =
+// the lane's source rows with the pixels outside the picture zeroed, mask = those pixels' byte masks, rcp / deq = the constants of all rungs
+// [n_rungs][64] (LDS), sums = the 64-bit sum of the wavefront's (stream, plane) at rung 0, PITCH words per rung.
 template <bool FLT, int LPM, int PITCH>
 __device__ __forceinline__ void rd_rung_loop(const f2 (&nn)[LPM == 8 ? 2 : 1][8], const uint4 (&a)[LPM == 8 ? 2 : 1], const uint4 (&mask)[LPM == 8 ? 2 : 1],
                                              const float *rcp, const int *deq, int n_rungs, int lane, int *xw, unsigned long long *__restrict__ sums)
@@ -111,17 +123,26 @@ __device__ __forceinline__ void rd_rung_loop(const f2 (&nn)[LPM == 8 ? 2 : 1][8]
         uint32_t ab = 0, bb = 0;
 #pragma unroll
         for (int pass = 0; pass < kPasses; pass++) {
-            uint4 b = rd_recon_row<FLT>(nn[pass], rcp + 64 * r, deq + 64 * r, xw, slot, i);
-            b = make_uint4(b.x & mask[pass].x, b.y & mask[pass].y, b.z & mask[pass].z, b.w & mask[pass].w);
+            const uint4 b = and4(rd_recon_row<FLT>(nn[pass], rcp + 64 * r, deq + 64 * r, xw, slot, i), mask[pass]);
             ab = dot_ab(a[pass], b.x, b.y, b.z, b.w, ab);
             bb = sq4(b.x, b.y, b.z, b.w, bb);
         }
-        const int mine = mb_sum((int)(aa + bb - 2u * ab));   // a lane: < 32 x 255^2; a macroblock: < 2^24
-        uint32_t total = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) total += (uint32_t)__builtin_amdgcn_readlane(mine, 8 * j);
-        if (lane == 0 && total) atomicAdd(&sums[(size_t)r * PITCH], (unsigned long long)total);
+        rd_sse_out(aa + bb - 2u * ab, lane, &sums[(size_t)r * PITCH]);
     }
+}
+
+// Both table sets an i-frame uses (luma, chroma), reciprocals and dequantiser products (f32 bits in the float form: deq < 2^24, checked on the
+// host) of all rungs: the workgroup's copy, made before any wavefront leaves (k_probe_iframe_rd, k_probe_iframe_ssim)
+template <bool FLT>
+__device__ __forceinline__ void rd_stage_intra_tables(const QTab *qtabs, int n_rungs, float (&rcp)[2][kProbeMaxRungs][64], int (&deq)[2][kProbeMaxRungs][64])
+{
+    for (int e = (int)threadIdx.x; e < n_rungs * 128; e += kThreads) {
+        const int r = e >> 7, sel = (e >> 6) & 1, j = e & 63;
+        const QTab *qt = qtabs + 4 * r + sel;
+        rcp[sel][r][j] = qt->rcp[j];
+        deq[sel][r][j] = FLT ? __float_as_int((float)qt->deq[j]) : qt->deq[j];
+    }
+    __syncthreads();
 }
 
 template <bool FLT, int LPM = 8>
@@ -134,85 +155,39 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe_rd(FrameGeom g, const
     __shared__ int deq_lds[2][kProbeMaxRungs][64];
     constexpr int kPasses = LPM == 8 ? 2 : 1;
 
-    // the workgroup's copy of both table sets, before any wavefront leaves
-    for (int e = (int)threadIdx.x; e < n_rungs * 128; e += kThreads) {
-        const int r = e >> 7, sel = (e >> 6) & 1, j = e & 63;
-        const QTab *qt = qtabs + 4 * r + sel;
-        rcp_lds[sel][r][j] = qt->rcp[j];
-        deq_lds[sel][r][j] = FLT ? __float_as_int((float)qt->deq[j]) : qt->deq[j];   // float form: deq < 2^24 (checked on the host)
-    }
-    __syncthreads();
-
+    rd_stage_intra_tables<FLT>(qtabs, n_rungs, rcp_lds, deq_lds);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int gw = xcd_remap((int)blockIdx.x, (int)gridDim.x) * kStripsPerWG + wave;
     const int gstrip = LPM == 8 ? gw : gw >> 1, half_strip = LPM == 8 ? 0 : gw & 1;
     if (gstrip >= g.strips_per_frame * g.n_streams) return;   // no cross-wavefront sync from here on
     const StripPos sp = locate_strip(g, gstrip);
     if (half_strip * 4 >= sp.n_mb) return;
+    const int m = LPM == 8 ? lane >> 3 : half_strip * 4 + (lane >> 4);   // macroblock within the strip
+    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + g.p[sp.plane].qsel, lane);
     const PlaneGeom &p = g.p[sp.plane];
-    const int slot = lane >> 3, i = lane & 7;
-    const int m = LPM == 8 ? slot : half_strip * 4 + (slot >> 1);   // macroblock within the strip
-    int *xw = xchg[wave];
-
-    // scale and zigzag position do not depend on the rung (the entry's reciprocal and dequantiser are rung 0's and are not used)
-    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + p.qsel, lane);
-    const uint8_t *plane = frame_src(g, src, sp.stream) + p.src_off;
     uint4 rows[kPasses], mask[kPasses];
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) {
-        const int x = sp.x0 + m * 16, y = sp.y0 + i + 8 * (LPM == 8 ? pass : (slot & 1));
-        rows[pass] = load_src16(plane, p, x, y);
-        mask[pass] = rd_picture_mask(p, x, y);
-    }
-    wave_lds_sync();
-    const LaneQ lq{qtab_lds[wave], i};
-
-    // n = (m * SCALE) >> 16 of the lane's subblocks, column layout, as k_probe_iframe
     f2 nn[kPasses][8];
-    int *mb = xw + slot * kMBPitch;
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) {
-        if (FLT) {
-            f2 x[8];
-            unpack_row_f(rows[pass], x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) x[k] = x[k] * f2s(256.0f) - f2s(32768.0f);   // (px - 128) << 8, src/common.rs:291
-            ffdct8(x);
-            f_rows_to_cols(x, mb, i, slot & 3);
-            ffdct8(x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) nn[pass][k] = quant_scale(x[k], lq.scale(k));
-        } else {   // forward_half's arithmetic
-            int v[2][8];
-            unpack_row(rows[pass], v);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[s][k] = (int)((unsigned)(v[s][k] - 128) << 8);
-            }
-            fdct8(v[0]);
-            fdct8(v[1]);
-            rows_to_cols2(v, mb, i, slot & 3);
-            fdct8(v[0]);
-            fdct8(v[1]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int scale = lq.scale(k);
-                nn[pass][k] = f2{(float)(wmul24(v[0][k], scale) >> 16), (float)(wmul24(v[1][k], scale) >> 16)};
-            }
-        }
-    }
     int zz[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
+    for (int pass = 0; pass < kPasses; pass++) mask[pass] = rd_picture_mask(p, sp.x0 + m * 16, probe_strip_y<LPM>(sp, lane, pass));
+    probe_strip_front<FLT, LPM>(g, src, sp, m, lane, qtab_lds[wave], xchg[wave], rows, nn, zz);
     const bool present = m < sp.n_mb;   // macroblocks beyond the strip's end count nothing (and lie outside the picture: their mask is empty)
     probe_rung_loop<LPM, kProbeAcc, kProbeStats>(nn, zz, &rcp_lds[p.qsel][0][0], n_rungs, lane, acc + (size_t)sp.stream * n_rungs * kProbeAcc,
                                                  [&](int) { return present; });
 #pragma unroll
-    for (int pass = 0; pass < kPasses; pass++)
-        rows[pass] = make_uint4(rows[pass].x & mask[pass].x, rows[pass].y & mask[pass].y, rows[pass].z & mask[pass].z, rows[pass].w & mask[pass].w);
-    rd_rung_loop<FLT, LPM, 3>(nn, rows, mask, &rcp_lds[p.qsel][0][0], &deq_lds[p.qsel][0][0], n_rungs, lane, xw,
+    for (int pass = 0; pass < kPasses; pass++) rows[pass] = and4(rows[pass], mask[pass]);
+    rd_rung_loop<FLT, LPM, 3>(nn, rows, mask, &rcp_lds[p.qsel][0][0], &deq_lds[p.qsel][0][0], n_rungs, lane, xchg[wave],
                               sse_acc + ((size_t)sp.stream * n_rungs) * 3 + sp.plane);
+}
+
+// the three plane sums of the wavefront's (stream, rung) moved to the caller's buffer and cleared: the tail of both *_rd_sizes kernels
+__device__ __forceinline__ void rd_sums_out(unsigned long long *__restrict__ sse_acc, unsigned long long *__restrict__ sse)
+{
+    const size_t at = (size_t)blockIdx.x * 3 + threadIdx.x;
+    if (threadIdx.x < 3) {
+        sse[at] = sse_acc[at];
+        sse_acc[at] = 0;   // consumed: the next call starts clean
+    }
 }
 
 // One wavefront per (stream, rung): k_probe_sizes's row, then the plane sums of the same (stream, rung) out and cleared
@@ -224,11 +199,7 @@ __global__ __launch_bounds__(64) void k_probe_rd_sizes(uint32_t *__restrict__ ac
     __shared__ uint8_t len[16], table[16];
     __shared__ int parent[32], branch[32];
     probe_sizes_row<false>(acc, sizes, stats, hist, table, val, len, parent, branch);
-    const size_t at = (size_t)blockIdx.x * 3 + threadIdx.x;
-    if (threadIdx.x < 3) {
-        sse[at] = sse_acc[at];
-        sse_acc[at] = 0;   // consumed: the next call starts clean
-    }
+    rd_sums_out(sse_acc, sse);
 }
 
 }  // namespace pfv

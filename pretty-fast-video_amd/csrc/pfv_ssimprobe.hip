@@ -18,109 +18,75 @@ static int ssim_probe_map(pfv_enc_session *s, bool pframe, const char *who)
     return PFV_OK;
 }
 
-// slots [win_first, win_first + win_count), as rd_probe_launch / prd_probe_launch: the probe kernel, the windows, the RD probes' tail
+// the probe kernel, the windows, the RD probes' tail
 static int ssim_probe_launch(pfv_enc_session *s, bool pframe, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, int64_t *ssim_dev, uint32_t *stats_dev)
 {
     pfv_ctx *ctx = s->ctx;
     int rc = ssim_probe_map(s, pframe, pframe ? "pfv_enc_probe_pframe_ssim_dev" : "pfv_enc_probe_iframe_ssim_dev");
     if (rc) return rc;
-    const size_t first = (size_t)s->win_first, R = (size_t)s->n_rungs;
-    const size_t stride = s->in_stride ? s->in_stride : (size_t)s->geom.src_frame_bytes;
-    const uint8_t *src = frames_dev + first * stride;
-    const FrameGeom g = enc_win_geom(s, s->win_count, src);
-    unsigned long long *sse_acc = (unsigned long long *)s->rd_acc + first * R * 3;
-    uint32_t *map = s->ssim_probe_map + first * ssim_map_stream_dwords(g.mbs_per_frame, s->n_rungs);
+    const ProbeWin w = probe_win(s, frames_dev, pframe);
     const QTab *qt = (const QTab *)s->qtab_dev;
-    const unsigned rows = (unsigned)((size_t)s->win_count * R);
-    uint32_t *acc;
+    unsigned long long *sse_acc = (unsigned long long *)s->rd_acc + w.first * w.R * 3, *sse_out = (unsigned long long *)sse_dev + w.first * w.R * 3;
+    uint32_t *map = s->ssim_probe_map + w.first * ssim_map_stream_dwords(w.g.mbs_per_frame, s->n_rungs);
+    uint32_t *acc = pframe ? s->pprobe_acc + w.first * w.R * kPProbeAcc : s->probe_acc + w.first * w.R * kProbeAcc;
+    const unsigned rows = (unsigned)((size_t)s->win_count * w.R);
     if (pframe) {
-        const uint8_t *ref = s->prev[s->cur] + first * (size_t)s->geom.pad_frame_bytes;
-        acc = s->pprobe_acc + first * R * kPProbeAcc;
-        const float *min_err = reinterpret_cast<const float *>(s->pprobe_acc + (size_t)s->n_streams * R * kPProbeAcc);
-        if (s->flt) hipLaunchKernelGGL(k_probe_pframe_ssim<true>, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, src, ref, qt, s->n_rungs, min_err, -2, acc, sse_acc, map);
-        else hipLaunchKernelGGL(k_probe_pframe_ssim<false>, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, src, ref, qt, s->n_rungs, min_err, -2, acc, sse_acc, map);
+        if (s->flt) hipLaunchKernelGGL(k_probe_pframe_ssim<true>, dim3(penc_blocks(ctx, w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, w.ref, qt, s->n_rungs, w.min_err, -2, acc, sse_acc, map);
+        else hipLaunchKernelGGL(k_probe_pframe_ssim<false>, dim3(penc_blocks(ctx, w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, w.ref, qt, s->n_rungs, w.min_err, -2, acc, sse_acc, map);
+    } else if (use_small_grid(s->lane_mapping, w.g)) {
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_ssim<true, 16>), dim3(half_strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc, map);
+        else hipLaunchKernelGGL((k_probe_iframe_ssim<false, 16>), dim3(half_strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc, map);
     } else {
-        acc = s->probe_acc + first * R * kProbeAcc;
-        if (use_small_grid(s->lane_mapping, g)) {
-            if (s->flt) hipLaunchKernelGGL((k_probe_iframe_ssim<true, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc, map);
-            else hipLaunchKernelGGL((k_probe_iframe_ssim<false, 16>), dim3(half_strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc, map);
-        } else {
-            if (s->flt) hipLaunchKernelGGL((k_probe_iframe_ssim<true, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc, map);
-            else hipLaunchKernelGGL((k_probe_iframe_ssim<false, 8>), dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, qt, s->n_rungs, acc, sse_acc, map);
-        }
+        if (s->flt) hipLaunchKernelGGL((k_probe_iframe_ssim<true, 8>), dim3(strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc, map);
+        else hipLaunchKernelGGL((k_probe_iframe_ssim<false, 8>), dim3(strip_blocks(w.g)), dim3(kThreads), 0, ctx->stream, w.g, w.src, qt, s->n_rungs, acc, sse_acc, map);
     }
-    hipLaunchKernelGGL(k_probe_ssim_windows, dim3(rows), dim3(kThreads), 0, ctx->stream, g, s->n_rungs, (const uint32_t *)map, ssim_dev + first * R * 3);
+    hipLaunchKernelGGL(k_probe_ssim_windows, dim3(rows), dim3(kThreads), 0, ctx->stream, w.g, s->n_rungs, (const uint32_t *)map, ssim_dev + w.first * w.R * 3);
     if (pframe)
-        hipLaunchKernelGGL(k_pprobe_rd_sizes, dim3(rows), dim3(64), 0, ctx->stream, acc, sizes_dev + first * R,
-                           stats_dev ? stats_dev + first * R * kPProbeStats : (uint32_t *)nullptr, sse_acc, (unsigned long long *)sse_dev + first * R * 3);
+        hipLaunchKernelGGL(k_pprobe_rd_sizes, dim3(rows), dim3(64), 0, ctx->stream, acc, sizes_dev + w.first * w.R,
+                           stats_dev ? stats_dev + w.first * w.R * kPProbeStats : (uint32_t *)nullptr, sse_acc, sse_out);
     else
-        hipLaunchKernelGGL(k_probe_rd_sizes, dim3(rows), dim3(64), 0, ctx->stream, acc, sizes_dev + first * R,
-                           stats_dev ? stats_dev + first * R * kProbeStats : (uint32_t *)nullptr, sse_acc, (unsigned long long *)sse_dev + first * R * 3);
+        hipLaunchKernelGGL(k_probe_rd_sizes, dim3(rows), dim3(64), 0, ctx->stream, acc, sizes_dev + w.first * w.R,
+                           stats_dev ? stats_dev + w.first * w.R * kProbeStats : (uint32_t *)nullptr, sse_acc, sse_out);
     return launch_check(ctx, pframe ? "k_probe_pframe_ssim / k_probe_ssim_windows / k_pprobe_rd_sizes" : "k_probe_iframe_ssim / k_probe_ssim_windows / k_probe_rd_sizes");
 }
 
 // the frames in the session's staging (all slots, packed) -> sizes_out [n_streams][n_rungs], sse_out and ssim_out [n_streams][n_rungs][3] and,
-// where asked for (p-frames), counts_out [n_streams][n_rungs][kPProbeStats]; one download of 52 bytes per (stream, rung) -- both sums first,
-// so that every part stays aligned --, the counts behind them where asked for, and one synchronisation
+// where asked for (p-frames), counts_out [n_streams][n_rungs][kPProbeStats]: 52 bytes per (stream, rung), the counts behind them, through
+// probe_download
 static int ssim_probe_staged(pfv_enc_session *s, bool pframe, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_out, uint32_t *counts_out = nullptr)
 {
     pfv_ctx *ctx = s->ctx;
     const size_t n = (size_t)s->n_streams * (size_t)s->n_rungs;
     const size_t sum_bytes = n * 3 * sizeof(uint64_t), size_bytes = n * sizeof(uint32_t), stat_bytes = n * kPProbeStats * sizeof(uint32_t);
     if (!s->ssim_probe_out) HIP_TRY(ctx, hipMalloc((void **)&s->ssim_probe_out, 2 * sum_bytes + size_bytes + stat_bytes));
-    const size_t bytes = 2 * sum_bytes + size_bytes + (counts_out ? stat_bytes : 0);
-    std::vector<uint8_t> host(bytes);
     uint8_t *out = (uint8_t *)s->ssim_probe_out;
     uint32_t *sizes_dev = (uint32_t *)(out + 2 * sum_bytes);
     int rc = ssim_probe_launch(s, pframe, s->st_frames, sizes_dev, (uint64_t *)out, (int64_t *)(out + sum_bytes), counts_out ? sizes_dev + n : nullptr);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(host.data(), out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(sse_out, host.data(), sum_bytes);
-    memcpy(ssim_out, host.data() + sum_bytes, sum_bytes);
-    memcpy(sizes_out, host.data() + 2 * sum_bytes, size_bytes);
-    if (counts_out) memcpy(counts_out, host.data() + 2 * sum_bytes + size_bytes, stat_bytes);
-    return PFV_OK;
-}
-static int ssim_probe_dev(pfv_enc_session *s, bool pframe, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, int64_t *ssim_q24_dev, uint32_t *stats_dev, const char *who)
-{
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames_dev || !sizes_dev || !sse_dev || !ssim_q24_dev) return fail(ctx, PFV_ERR_BAD_ARG, std::string(who) + ": null buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ssim_probe_launch(s, pframe, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev);
-}
-static int ssim_probe_host(pfv_enc_session *s, bool pframe, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out, const char *who)
-{
-    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    pfv_ctx *ctx = s->ctx;
-    if (!frames || !sizes_out || !sse_out || !ssim_q24_out) return fail(ctx, PFV_ERR_BAD_ARG, std::string(who) + ": null buffer");
-    if (!enc_full_window(s)) return fail(ctx, PFV_ERR_STATE, std::string(who) + ": the host-buffer entry points work on all slots, packed (reset the window / frame stride)");
-    if (ctx->capturing) return fail(ctx, PFV_ERR_STATE, std::string(who) + ": host-pointer entry points cannot be recorded");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = enc_staging(s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s->st_frames, frames, (size_t)s->geom.src_frame_bytes * s->n_streams, hipMemcpyHostToDevice, ctx->stream));
-    return ssim_probe_staged(s, pframe, sizes_out, sse_out, ssim_q24_out);
+    return probe_download(ctx, out, n, sse_out, ssim_out, sizes_out, counts_out);
 }
 
 extern "C" {
 
 PFV_API int pfv_enc_probe_iframe_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, int64_t *ssim_q24_dev, uint32_t *stats_dev)
 {
-    return ssim_probe_dev(s, false, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev, "pfv_enc_probe_iframe_ssim_dev");
+    int rc = probe_dev_enter(s, frames_dev && sizes_dev && sse_dev && ssim_q24_dev, "pfv_enc_probe_iframe_ssim_dev");
+    return rc ? rc : ssim_probe_launch(s, false, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev);
 }
 PFV_API int pfv_enc_probe_iframe_ssim(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
 {
-    return ssim_probe_host(s, false, frames, sizes_out, sse_out, ssim_q24_out, "pfv_enc_probe_iframe_ssim");
+    int rc = probe_host_enter(s, frames, sizes_out && sse_out && ssim_q24_out, "pfv_enc_probe_iframe_ssim");
+    return rc ? rc : ssim_probe_staged(s, false, sizes_out, sse_out, ssim_q24_out);
 }
 PFV_API int pfv_enc_probe_pframe_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, int64_t *ssim_q24_dev, uint32_t *stats_dev)
 {
-    return ssim_probe_dev(s, true, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev, "pfv_enc_probe_pframe_ssim_dev");
+    int rc = probe_dev_enter(s, frames_dev && sizes_dev && sse_dev && ssim_q24_dev, "pfv_enc_probe_pframe_ssim_dev");
+    return rc ? rc : ssim_probe_launch(s, true, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev);
 }
 PFV_API int pfv_enc_probe_pframe_ssim(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
 {
-    return ssim_probe_host(s, true, frames, sizes_out, sse_out, ssim_q24_out, "pfv_enc_probe_pframe_ssim");
+    int rc = probe_host_enter(s, frames, sizes_out && sse_out && ssim_q24_out, "pfv_enc_probe_pframe_ssim");
+    return rc ? rc : ssim_probe_staged(s, true, sizes_out, sse_out, ssim_q24_out);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // wavefront that rebuilt it, and the p-frame probe's tile form does not keep neighbouring macroblocks in neighbouring wavefronts.  So the
 // probe kernels leave the 4 x 4 BLOCK SUMS of every rung in a map in scratch, and a second kernel forms the windows from it:
 //
-//   k_probe_iframe_ssim   k_probe_iframe_rd's strip mapping (both lane mappings), front end and size loop.  Its distortion loop per rung: the
+//   k_probe_iframe_ssim   rd_stage_intra_tables, probe_strip_front (both lane mappings), probe_rung_loop.  Its distortion loop per rung: the
 //                         reconstructed row of rd_recon_row, masked like the source row (rd_picture_mask), then per dword -- one block-row --
 //                         v_dot4_u32_u8 once each for sum b, sum b^2 and sum ab.  sum b (<= 4080) and sum b^2 (<= 1 040 400) of a block share
 //                         a dword (12 + 20 bits), sum ab (<= 1 040 400) takes the next.  The lane's squared error is the sum of the same terms,
@@ -18,7 +18,7 @@
 //                         one dword per block, [stream][macroblock][16], stored once.
 //                         The masks cost the block sums nothing: a window exists only when all 64 of its pixels lie inside the picture (the
 //                         argument at the head of k_ssim_mb), so a block that the mask touches belongs to no window.
-//   k_probe_pframe_ssim   the same behind k_probe_pframe_rd's front end (8 lanes per macroblock only).  A macroblock skipped at rung r stores
+//   k_probe_pframe_ssim   the same behind probe_tile_front<FLT, true> (8 lanes per macroblock only).  A macroblock skipped at rung r stores
 //                         the block sums of its patch, formed once before the rung loop like skip_sse; a coded one those of
 //                         rd_recon_row<FLT, true>.  The wavefront-uniform early-out of a rung at which nothing is coded stays; the stores happen.
 //   k_probe_ssim_windows  one workgroup per (stream of the window, rung); 8 lanes per macroblock of the frame (all planes) read the map back as it
@@ -89,17 +89,6 @@ __device__ __forceinline__ unsigned ssim_src_row(const uint4 &a, int j, unsigned
     }
     return quad_col_sum(p0, j);
 }
-__device__ __forceinline__ uint4 and4(const uint4 &x, const uint4 &m) { return make_uint4(x.x & m.x, x.y & m.y, x.z & m.z, x.w & m.w); }
-
-// the wavefront's sum of the lanes' squared errors into the plane sum of rung r (rd_rung_loop's tail)
-__device__ __forceinline__ void ssim_probe_sse_out(uint32_t lane_sse, int lane, unsigned long long *sum)
-{
-    const int mine = mb_sum((int)lane_sse);   // a lane: < 32 x 255^2; a macroblock: < 2^24; the wavefront: < 2^27
-    uint32_t total = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) total += (uint32_t)__builtin_amdgcn_readlane(mine, 8 * j);
-    if (lane == 0 && total) atomicAdd(sum, (unsigned long long)total);
-}
 
 template <bool FLT, int LPM = 8>
 __global__ __launch_bounds__(kThreads) void k_probe_iframe_ssim(FrameGeom g, const uint8_t *__restrict__ src, const QTab *__restrict__ qtabs, int n_rungs,
@@ -111,79 +100,25 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe_ssim(FrameGeom g, con
     __shared__ int deq_lds[2][kProbeMaxRungs][64];
     constexpr int kPasses = LPM == 8 ? 2 : 1;
 
-    // the workgroup's copy of both table sets, before any wavefront leaves (as k_probe_iframe_rd)
-    for (int e = (int)threadIdx.x; e < n_rungs * 128; e += kThreads) {
-        const int r = e >> 7, sel = (e >> 6) & 1, j = e & 63;
-        const QTab *qt = qtabs + 4 * r + sel;
-        rcp_lds[sel][r][j] = qt->rcp[j];
-        deq_lds[sel][r][j] = FLT ? __float_as_int((float)qt->deq[j]) : qt->deq[j];   // float form: deq < 2^24 (checked on the host)
-    }
-    __syncthreads();
-
+    rd_stage_intra_tables<FLT>(qtabs, n_rungs, rcp_lds, deq_lds);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int gw = xcd_remap((int)blockIdx.x, (int)gridDim.x) * kStripsPerWG + wave;
     const int gstrip = LPM == 8 ? gw : gw >> 1, half_strip = LPM == 8 ? 0 : gw & 1;
     if (gstrip >= g.strips_per_frame * g.n_streams) return;   // no cross-wavefront sync from here on
     const StripPos sp = locate_strip(g, gstrip);
     if (half_strip * 4 >= sp.n_mb) return;
+    const int m = LPM == 8 ? lane >> 3 : half_strip * 4 + (lane >> 4);   // macroblock within the strip
+    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + g.p[sp.plane].qsel, lane);
     const PlaneGeom &p = g.p[sp.plane];
     const int slot = lane >> 3, i = lane & 7;
-    const int m = LPM == 8 ? slot : half_strip * 4 + (slot >> 1);   // macroblock within the strip
     int *xw = xchg[wave];
-
-    fill_qtable<true, FLT>(qtab_lds[wave], qtabs + p.qsel, lane);
-    const uint8_t *plane = frame_src(g, src, sp.stream) + p.src_off;
     uint4 rows[kPasses], mask[kPasses];
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) {
-        const int x = sp.x0 + m * 16, y = sp.y0 + i + 8 * (LPM == 8 ? pass : (slot & 1));
-        rows[pass] = load_src16(plane, p, x, y);
-        mask[pass] = rd_picture_mask(p, x, y);
-    }
-    wave_lds_sync();
-    const LaneQ lq{qtab_lds[wave], i};
-
-    // n = (m * SCALE) >> 16 of the lane's subblocks, column layout, as k_probe_iframe
     f2 nn[kPasses][8];
-    int *mb = xw + slot * kMBPitch;
-#pragma unroll
-    for (int pass = 0; pass < kPasses; pass++) {
-        if (FLT) {
-            f2 x[8];
-            unpack_row_f(rows[pass], x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) x[k] = x[k] * f2s(256.0f) - f2s(32768.0f);   // (px - 128) << 8, src/common.rs:291
-            ffdct8(x);
-            f_rows_to_cols(x, mb, i, slot & 3);
-            ffdct8(x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) nn[pass][k] = quant_scale(x[k], lq.scale(k));
-        } else {   // forward_half's arithmetic
-            int v[2][8];
-            unpack_row(rows[pass], v);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[s][k] = (int)((unsigned)(v[s][k] - 128) << 8);
-            }
-            fdct8(v[0]);
-            fdct8(v[1]);
-            rows_to_cols2(v, mb, i, slot & 3);
-            fdct8(v[0]);
-            fdct8(v[1]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int scale = lq.scale(k);
-                nn[pass][k] = f2{(float)(wmul24(v[0][k], scale) >> 16), (float)(wmul24(v[1][k], scale) >> 16)};
-            }
-        }
-    }
     int zz[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
+    probe_strip_front<FLT, LPM>(g, src, sp, m, lane, qtab_lds[wave], xw, rows, nn, zz);
     const bool present = m < sp.n_mb;   // macroblocks beyond the strip's end count nothing and store nothing
-    // distortion and block sums, BEFORE the size loop (below).  The lane's place in a macroblock's part of the map: 4 dwords per lane i, of which the 16-lane mapping's
-    // second row half (slot & 1: block rows 2 and 3) takes the upper two
+    // distortion and block sums, in front of the size loop.  The lane's place in a macroblock's part of the map: 4 dwords per lane i, of which
+    // the 16-lane mapping's second row half (slot & 1: block rows 2 and 3) takes the upper two
     const size_t mbs = (size_t)g.mbs_per_frame, mbi = (size_t)(sp.mb_first + m);
     uint32_t *smap = map + (size_t)sp.stream * ssim_map_stream_dwords(g.mbs_per_frame, n_rungs);
     uint32_t *src_at = smap + mbi * kSsimMapSrc + i * 2 + (LPM == 8 ? 0 : (slot & 1));
@@ -192,6 +127,7 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe_ssim(FrameGeom g, con
     uint32_t sw[kPasses];
 #pragma unroll
     for (int pass = 0; pass < kPasses; pass++) {
+        mask[pass] = rd_picture_mask(p, sp.x0 + m * 16, probe_strip_y<LPM>(sp, lane, pass));
         rows[pass] = and4(rows[pass], mask[pass]);
         sw[pass] = ssim_src_row(rows[pass], i & 3, aa);
     }
@@ -214,12 +150,9 @@ __global__ __launch_bounds__(kThreads) void k_probe_iframe_ssim(FrameGeom g, con
             if (LPM == 8) *reinterpret_cast<uint4 *>(at) = make_uint4(w[0][0], w[0][1], w[kPasses - 1][0], w[kPasses - 1][1]);
             else *reinterpret_cast<uint2 *>(at) = make_uint2(w[0][0], w[0][1]);
         }
-        ssim_probe_sse_out(aa + bb - 2u * ab, lane, &sums[(size_t)r * 3]);
+        rd_sse_out(aa + bb - 2u * ab, lane, &sums[(size_t)r * 3]);
     }
-    // sizes and counts behind the distortion loop, as k_probe_pframe_rd orders them: the source rows and masks end above, and kept alive across
-    // probe_rung_loop they cost the 8-lane form its second wavefront per SIMD (258 registers against 256)
-    probe_rung_loop<LPM, kProbeAcc, kProbeStats>(nn, zz, &rcp_lds[p.qsel][0][0], n_rungs, lane, acc + (size_t)sp.stream * n_rungs * kProbeAcc,
-                                                 [&](int) { return present; });
+    probe_rung_loop<LPM, kProbeAcc, kProbeStats>(nn, zz, rcp, n_rungs, lane, acc + (size_t)sp.stream * n_rungs * kProbeAcc, [&](int) { return present; });
 }
 
 template <bool FLT>
@@ -233,83 +166,26 @@ __global__ __launch_bounds__(kThreads) void k_probe_pframe_ssim(FrameGeom g, con
     __shared__ float rcp_lds[kProbeMaxRungs][64];
     __shared__ int deq_lds[kProbeMaxRungs][64];
     __shared__ float err_lds[kProbeMaxRungs];
-    uint8_t *win = win_lds + 16;
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int m = lane >> 3, i = lane & 7;
-    const int vt = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const TilePos cur = locate_tile(g, vt, wave);
-    const PlaneGeom &p = g.p[cur.sp.plane];
-    // as k_probe_pframe_rd
-    if (wave == 0) {
-        fill_qtable<true, FLT>(qtab_lds, qtabs + 2 + p.qsel, lane);
-        if (lane < n_rungs) err_lds[lane] = min_err[lane];
-    }
-    for (int r = wave; r < n_rungs; r += kStripsPerWG) {
-        const QTab *qt = qtabs + 4 * r + 2 + p.qsel;
-        rcp_lds[r][lane] = qt->rcp[lane];
-        deq_lds[r][lane] = FLT ? __float_as_int((float)qt->deq[lane]) : qt->deq[lane];   // float form: deq < 2^24 (checked on the host)
-    }
-    issue_window(p, ref + (long)cur.sp.stream * g.pad_frame_bytes + p.pad_off, cur, win, wave, lane);
     uint4 rows[2];
-    rows[0] = rows[1] = make_uint4(0, 0, 0, 0);
-    if (cur.wave_valid) {
-        const uint8_t *plane = frame_src(g, src, cur.sp.stream) + p.src_off;
-        rows[0] = load_src16(plane, p, cur.sp.x0 + m * 16, cur.sp.y0 + i);
-        rows[1] = load_src16(plane, p, cur.sp.x0 + m * 16, cur.sp.y0 + i + 8);
-    }
-    __syncthreads();   // window complete (vmcnt drained at the barrier); the tables are visible
     SearchOut so;
-    so.cx = so.cy = so.err = 0; so.coded = false;
-    so.patch[0] = so.patch[1] = make_uint4(0, 0, 0, 0);
-    if (cur.wave_valid) penc_search<true>(g, cur, win, red_lds, rows, lane, 0.0f, neg2, so);   // the skip test is taken per rung below
-    __syncthreads();   // window released by every wavefront: its slices become the exchange regions
+    int *xw;
+    const TilePos cur = probe_tile_front<FLT, true>(g, src, ref, qtabs, n_rungs, min_err, neg2, win_lds + 16, red_lds, qtab_lds, rcp_lds, deq_lds, err_lds, lane, wave, rows, so, xw);
     if (!cur.wave_valid) return;   // no barrier behind this point
 
-    int *xw = reinterpret_cast<int *>(win + win_first_issue(wave) * 1024);
-    int *mb = xw + m * kMBPitch;
+    const PlaneGeom &p = g.p[cur.sp.plane];
     const LaneQ lq{qtab_lds, i};
-    // n = (m * SCALE) >> 16 of the residual, column layout, as k_probe_pframe
     f2 nn[2][8];
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-        if (FLT) {
-            f2 x[8], pp[8];
-            unpack_row_f(rows[h], x);
-            unpack_row_f(so.patch[h], pp);
-#pragma unroll
-            for (int k = 0; k < 8; k++) x[k] = residual_f(x[k], pp[k]);   // calc_residuals (:118-119), delta / 2 truncating, << 8 (:304)
-            ffdct8(x);
-            f_rows_to_cols(x, mb, i, m & 3);
-            ffdct8(x);
-#pragma unroll
-            for (int k = 0; k < 8; k++) nn[h][k] = quant_scale(x[k], lq.scale(k));
-        } else {   // penc_half's integer arithmetic
-            int v[2][8], pp[2][8];
-            unpack_row(rows[h], v);
-            unpack_row(so.patch[h], pp);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[s][k] = (int)((unsigned)tdiv2(v[s][k] - pp[s][k]) << 8);
-            }
-            fdct8(v[0]);
-            fdct8(v[1]);
-            rows_to_cols2(v, mb, i, m & 3);
-            fdct8(v[0]);
-            fdct8(v[1]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int scale = lq.scale(k);
-                nn[h][k] = f2{(float)(wmul24(v[0][k], scale) >> 16), (float)(wmul24(v[1][k], scale) >> 16)};
-            }
-        }
-    }
+    for (int h = 0; h < 2; h++) probe_forward_row<FLT, true>(rows[h], so.patch[h], xw + m * kMBPitch, i, m & 3, lq, nn[h]);
     const bool mb_valid = m < cur.sp.n_mb;   // macroblocks beyond the strip's end count nothing and store nothing
     const float err = (float)so.err;
+    const auto coded_at = [&](int r) { return mb_valid && !(err <= err_lds[r]); };   // the skip decision (:209, :221) at rung r
 
-    // distortion and block sums, BEFORE the size loop for k_probe_pframe_rd's reason: the source and patch rows end here.  The patch's block
-    // sums and squared error are the same at every rung: what a skipped macroblock stores and adds
+    // distortion and block sums, in front of the size loop.  The patch's block sums and squared error are the same at every rung: what a
+    // skipped macroblock stores and adds
     const size_t mbs = (size_t)g.mbs_per_frame, mbi = (size_t)(cur.sp.mb_first + m);
     uint32_t *smap = map + (size_t)cur.sp.stream * ssim_map_stream_dwords(g.mbs_per_frame, n_rungs);
     uint32_t *rec_at = smap + mbs * kSsimMapSrc + mbi * kSsimMapRec + i * 4;
@@ -326,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void k_probe_pframe_ssim(FrameGeom g, con
     const uint32_t skip_sse = aa + skip_bb - 2u * skip_ab;
     unsigned long long *sums = sse_acc + ((size_t)cur.sp.stream * n_rungs) * 3 + cur.sp.plane;
     for (int r = 0; r < n_rungs; r++) {
-        const bool coded = mb_valid && !(err <= err_lds[r]);
+        const bool coded = coded_at(r);
         uint32_t lane_sse = skip_sse;
         uint4 out = make_uint4(skip_w[0][0], skip_w[0][1], skip_w[1][0], skip_w[1][1]);
         if (__ballot(coded) != 0ull) {   // wavefront-uniform: the transposes and the quads' sums below need all 64 lanes
@@ -342,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void k_probe_pframe_ssim(FrameGeom g, con
             }
         }
         if (mb_valid) *reinterpret_cast<uint4 *>(rec_at + (size_t)r * mbs * kSsimMapRec) = out;
-        ssim_probe_sse_out(lane_sse, lane, &sums[(size_t)r * 3]);
+        rd_sse_out(lane_sse, lane, &sums[(size_t)r * 3]);
     }
 
     // sizes and counts: the size probe's own loops over the same registers
@@ -350,18 +226,8 @@ __global__ __launch_bounds__(kThreads) void k_probe_pframe_ssim(FrameGeom g, con
 #pragma unroll
     for (int k = 0; k < 8; k++) zz[k] = lq.zz(k);
     uint32_t *rows_acc = acc + (size_t)cur.sp.stream * n_rungs * kPProbeAcc;
-    probe_rung_loop<8, kPProbeAcc, kPProbeStats>(nn, zz, &rcp_lds[0][0], n_rungs, lane, rows_acc,
-                                                 [&](int r) { return mb_valid && !(err <= err_lds[r]); });   // the skip decision (:209, :221) at rung r
-
-    // header bits and the coded count per rung, as k_probe_pframe
-    const bool first = mb_valid && i == 0, moved = first && (so.cx != 0 || so.cy != 0);
-    const uint32_t n_moved = (uint32_t)__builtin_popcountll(__ballot(moved));
-    const uint32_t hdr_bits = 2u * (uint32_t)__builtin_popcountll(__ballot(first)) + 14u * n_moved;
-    for (int r = 0; r < n_rungs; r++) {
-        const uint32_t n_coded = (uint32_t)__builtin_popcountll(__ballot(first && !(err <= err_lds[r])));
-        const uint32_t mine = lane == kPProbeCodedAt ? n_coded : (lane == kPProbeMovedAt ? n_moved : hdr_bits);
-        if (lane >= kPProbeCodedAt && lane <= kPProbeHdrAt && mine) atomicAdd(&rows_acc[(size_t)r * kPProbeAcc + lane], mine);
-    }
+    probe_rung_loop<8, kPProbeAcc, kPProbeStats>(nn, zz, &rcp_lds[0][0], n_rungs, lane, rows_acc, coded_at);
+    pprobe_header_tail(mb_valid, so, n_rungs, lane, rows_acc, coded_at);
 }
 
 // The two blocks lane `li` of the 8-lane mapping stored for macroblock `at` -- (li >> 2, li & 3) and ((li >> 2) + 2, li & 3) -- as window
