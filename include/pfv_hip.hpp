@@ -212,6 +212,48 @@ inline std::vector<uint8_t> frames_scale(Context &ctx, size_t sw, size_t sh, siz
     return out;
 }
 
+// pfv_denoiser (pfv_hip_ext.h, "denoising pre-filter"): the previous output and the primed flag of n_streams streams; destroy it before its context
+class Denoiser {
+  public:
+    Denoiser(Context &ctx, size_t width, size_t height, int n_streams = 1) : ctx_(ctx), width_(width), height_(height), n_(n_streams)
+    {
+        int rc = PFV_OK;
+        h_ = pfv_denoiser_create(ctx.handle(), (int)width, (int)height, n_streams, &rc);
+        if (!h_) ctx_.check(rc ? rc : PFV_ERR_BAD_ARG);
+    }
+    ~Denoiser() { pfv_denoiser_destroy(h_); }
+    Denoiser(const Denoiser &) = delete;
+    Denoiser &operator=(const Denoiser &) = delete;
+    pfv_denoiser *handle() const { return h_; }
+    size_t frame_bytes() const { return pfv_frame_bytes((int)width_, (int)height_); }
+    // per plane (Y, U, V), 0 .. 16, for the runs that follow
+    void set_strength(const std::array<uint8_t, 3> &spatial, const std::array<uint8_t, 3> &temporal) { ctx_.check(pfv_denoiser_set_strength(h_, spatial.data(), temporal.data())); }
+    void reset(int first_stream = 0, int n = -1) { ctx_.check(pfv_denoiser_reset(h_, first_stream, n < 0 ? n_ - first_stream : n)); }
+    // asynchronous on the context's stream, one k_denoise: device frames in (packed or padded, src_stride apart), packed device frames out
+    void run_dev(int first_stream, int n, const uint8_t *src_dev, uint8_t *dst_dev, bool commit = true, int src_layout = PFV_FRAME_PACKED, size_t src_stride = 0,
+                 size_t dst_stride = 0)
+    {
+        ctx_.check(pfv_denoiser_run_dev(h_, first_stream, n, src_dev, src_layout, src_stride, dst_dev, dst_stride, commit ? 1 : 0));
+    }
+
+  private:
+    Context &ctx_;
+    size_t width_, height_;
+    int n_;
+    pfv_denoiser *h_ = nullptr;
+};
+// packed frames, frame-major ([frame][stream]), through a fresh filter in order
+inline std::vector<uint8_t> frames_denoise(Context &ctx, size_t width, size_t height, const std::vector<uint8_t> &frames, const std::array<uint8_t, 3> &spatial,
+                                           const std::array<uint8_t, 3> &temporal, int n_streams = 1)
+{
+    const size_t fb = pfv_frame_bytes((int)width, (int)height);
+    if (!fb || n_streams <= 0 || frames.empty() || frames.size() % (fb * (size_t)n_streams)) throw std::invalid_argument("frames_denoise: frames must hold whole packed frames of every stream");
+    std::vector<uint8_t> out(frames.size());
+    ctx.check(pfv_frames_denoise(ctx.handle(), (int)width, (int)height, n_streams, (int)(frames.size() / (fb * (size_t)n_streams)), frames.data(), out.data(), spatial.data(),
+                                 temporal.data()));
+    return out;
+}
+
 class Encoder {
   public:
     Encoder(std::ostream &writer, size_t width, size_t height, uint32_t framerate, int quality, Context &ctx)
@@ -277,6 +319,12 @@ class Encoder {
         in_w_ = src_width ? src_width : width_;
         in_h_ = src_width ? src_height : height_;
         rgb_bytes_ = bpp * in_w_ * in_h_;
+    }
+    // the noise filter as the last input stage (behind set_input_rgb and set_input_size): strengths per plane, 0 .. 16; encode_* commit its
+    // state, probe_* do not
+    void set_denoise(bool on, const std::array<uint8_t, 3> &spatial = {0, 0, 0}, const std::array<uint8_t, 3> &temporal = {0, 0, 0})
+    {
+        ctx_.check(pfv_encoder_set_denoise(h_, on ? 1 : 0, spatial.data(), temporal.data()));
     }
     void encode_iframe_rgb(const std::vector<uint8_t> &picture)
     {

@@ -585,6 +585,74 @@ PFV_API int pfv_enc_scale_dev(pfv_enc_session *s, pfv_scaler *sc, const uint8_t 
  * the frames that pfv_frames_scale made.  src_w == 0 switches it off (src_h and kind are then ignored). */
 PFV_API int pfv_encoder_set_input_size(pfv_encoder *e, int src_w, int src_h, int kind);
 
+/* ------------------------------------------------------------------ denoising pre-filter  [B]
+ * k_enc_pframe skips a macroblock only when its best match lies below min_err, and an inter residual is quantised coarsely: sensor or grain
+ * noise of a few grey levels turns static areas from skipped macroblocks into coded ones, at every rung.  The format has no loop filter and no
+ * per-macroblock quantiser, so a PRE-filter on the encoder's input is the only lever -- and it keeps every parity with the reference: the
+ * stream is byte for byte that of the reference encoder fed the filtered frames.  The mirror of the out-of-loop deblocking above.  Off by
+ * default.
+ *
+ * The filter (normative).  Each plane of w x h 8-bit samples is filtered on its own, in i32 integers.  Two strengths per plane (Y, U, V), each
+ * 0 .. 16: spatial Ss and temporal St.  The ramp is the deblocking filter's shape -- full up to S, back to zero at 2S, so real edges and motion
+ * are left alone:
+ *     phi(d, S) = sign(d) * max(0, |d| - max(0, 2 * (|d| - S)))        phi(d, 0) = 0
+ *   Stage 1, spatial.   For the sample c at (x, y) and its eight neighbours n_k of the INPUT plane, with weights g = 2 for the four edge
+ *                       neighbours and g = 1 for the four diagonal ones; a neighbour outside w x h contributes 0 (the padding of a padded
+ *                       source never takes part):
+ *                           s = c + ((sum_k g_k * phi(n_k - c, Ss) + 8) >> 4)            >> arithmetic (floor)
+ *                       s lies between the minimum and the maximum of the 3 x 3 window: no clamp.  Stage 1 reads only the input, so it is
+ *                       order-free and independent of the launch shape.
+ *   Stage 2, temporal.  P is the stream's state at (x, y), the previous OUTPUT of this filter; tdiv truncates toward zero:
+ *                           out = s + tdiv(3 * phi(P - s, St), 4)                          lies between s and P: no clamp
+ *                       A stream that is not primed (after create or reset) skips stage 2: out = s.  A committed run writes `out` to the
+ *                       destination AND to the state and primes the stream; an uncommitted run writes only the destination and leaves
+ *                       state and priming alone.  Stage 2 is pointwise: the state is updated in place.
+ * Ss == St == 0: out equals the input byte for byte.  A constant plane stays constant; identical consecutive frames with St > 0 converge to
+ * themselves.
+ * One launch, k_denoise (csrc/pfv_denoise_kernels.hip), covers all planes of n streams.  Source: PACKED or PADDED frames with their own
+ * stream stride (pfv_frames_sse_dev); destination: PACKED frames dst_stride bytes apart (0 = back to back); exactly the frames' bytes are
+ * written.  16-byte stores where aligned, a byte path with the same result otherwise.  No atomics, a run allocates nothing.  The streams'
+ * `primed` flags live in device memory: create and reset clear them with stream-ordered memsets, a committed run that covers an unprimed
+ * stream sets its window's flags with a stream-ordered memset behind the kernel.  A steady-state run is therefore exactly one kernel node of a
+ * recorded graph; a run that would need that memset inside a graph recording returns PFV_ERR_STATE.  Measured on one MI355X: see
+ * profiles/denoise.md. */
+typedef struct pfv_denoiser pfv_denoiser;
+/* owns the state (n_streams x pfv_frame_bytes) and the flags; strengths start at 0.  NULL and *err on failure (err may be NULL); PFV_ERR_STATE
+ * inside a graph recording.  The denoiser belongs to the context and must be destroyed before it. */
+PFV_API pfv_denoiser *pfv_denoiser_create(pfv_ctx *ctx, int width, int height, int n_streams, int *err);
+PFV_API void pfv_denoiser_destroy(pfv_denoiser *dn);
+/* per plane (Y, U, V), for the runs that follow; a value above 16: PFV_ERR_BAD_ARG */
+PFV_API int pfv_denoiser_set_strength(pfv_denoiser *dn, const uint8_t spatial[3], const uint8_t temporal[3]);
+/* un-primes streams [first_stream, first_stream + n); stream-ordered */
+PFV_API int pfv_denoiser_reset(pfv_denoiser *dn, int first_stream, int n);
+/* streams [first_stream, first_stream + n): stream first_stream + k's frame is at src_dev + k * src_stride and dst_dev + k * dst_stride (0 =
+ * back to back in the layout).  Asynchronous on the context's stream.  PFV_ERR_BAD_ARG: a null pointer, a window outside n_streams, a layout
+ * that does not exist, strides below the frame size, source and destination ranges that overlap, either overlapping the state. */
+PFV_API int pfv_denoiser_run_dev(pfv_denoiser *dn, int first_stream, int n, const uint8_t *src_dev, int src_layout, size_t src_stride, uint8_t *dst_dev,
+                                 size_t dst_stride, int commit);
+/* host buffers, packed, frame-major ([frame][stream]): makes a denoiser, runs the frames in order, committed, and synchronises;
+ * PFV_ERR_STATE while a graph is being recorded */
+PFV_API int pfv_frames_denoise(pfv_ctx *ctx, int width, int height, int n_streams, int n_frames, const uint8_t *src, uint8_t *dst, const uint8_t spatial[3],
+                               const uint8_t temporal[3]);
+/* An encoder session's input, the mirror of pfv_enc_scale_dev: the frames (packed) of the slots of the session's current window -- slot k's at
+ * frames_dev + k * src_stride, 0 = pfv_frame_bytes -- are filtered as the denoiser's streams k into slot k's frame of a third packed buffer the
+ * session owns (n_streams x pfv_frame_bytes), one k_denoise; *frames_dev_out = that buffer's base, from that point of the stream on a valid
+ * `frames_dev` for every session entry point that takes one.  Frames of slots outside the window are left alone.  The buffer is allocated by
+ * the first call (PFV_ERR_STATE inside a graph recording).  PFV_ERR_STATE while a non-zero pfv_enc_session_set_frame_stride is set.  The
+ * denoiser's size, stream count and context must be the session's, else PFV_ERR_BAD_ARG; the session does not own the denoiser.
+ * pfv_gop_encoder and pfv_batch_encoder have no switch: their _dev forms take frames that pfv_denoiser_run_dev made. */
+PFV_API int pfv_enc_denoise_dev(pfv_enc_session *s, pfv_denoiser *dn, const uint8_t *frames_dev, size_t src_stride, int commit, const uint8_t **frames_dev_out);
+/* pfv_encoder: the last input stage, behind pfv_encoder_set_input_rgb and pfv_encoder_set_input_size: upload -> ingest -> scale -> denoise ->
+ * the session's frame staging.  Scratch and the denoiser (one stream, owned) are made by this call, never by an encode call.  The frame an
+ * encode_iframe / encode_pframe / encode_frame call uploads is filtered COMMITTED -- once per call: the budget and floor probes those calls run
+ * work on the staged, filtered frame -- and the frame one of the six pfv_encoder_probe_* calls uploads is filtered UNCOMMITTED, so a probe
+ * followed by the encode of the same picture shows the encoder the frame the probe saw.  The host entropy path brings the filtered planes back
+ * down as it does for RGB / resized input.  The stream, the rungs chosen, frame types, reports and frame SSIM are bit for bit those of an
+ * encoder fed the frames that pfv_frames_denoise makes of the same sequence.  Switching on (from off) un-primes the filter; `on` while on only
+ * changes the strengths.  A strength above 16 or null strengths with `on`: PFV_ERR_BAD_ARG.  Off ignores the strengths, and every call is what
+ * it is without the switch. */
+PFV_API int pfv_encoder_set_denoise(pfv_encoder *e, int on, const uint8_t spatial[3], const uint8_t temporal[3]);
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`

@@ -19,7 +19,8 @@ from .enc import BatchEncoder, Encoder, GopEncoder
 from .dec import BatchDecoder, Decoder, DecodeError, GopDecoder
 from .synth import SyntheticStream
 from .scale import Scaler, frames_scale, scale_table, scale_taps
+from .denoise import Denoiser, frames_denoise
 from .quality import FrameReport, FrameSsim, deblock_strength, frames_deblock, frames_from_rgb, frames_sse, frames_to_rgb, frames_ssim, psnr, ssim, ssim_windows
 
 __all__ = ["Context", "Graph", "VideoPlane", "VideoFrame", "EncodedIPlane", "EncodedPPlane", "EncoderSession",
-           "DecoderSession", "Encoder", "BatchEncoder", "GopEncoder", "Decoder", "BatchDecoder", "GopDecoder", "DecodeError", "qtables_from_quality", "PfvError", "SyntheticStream", "FrameReport", "frames_sse", "psnr", "FrameSsim", "frames_ssim", "ssim", "ssim_windows", "frames_deblock", "deblock_strength", "frames_to_rgb", "frames_from_rgb", "Scaler", "frames_scale", "scale_table", "scale_taps", "_lib"]
+           "DecoderSession", "Encoder", "BatchEncoder", "GopEncoder", "Decoder", "BatchDecoder", "GopDecoder", "DecodeError", "qtables_from_quality", "PfvError", "SyntheticStream", "FrameReport", "frames_sse", "psnr", "FrameSsim", "frames_ssim", "ssim", "ssim_windows", "frames_deblock", "deblock_strength", "frames_to_rgb", "frames_from_rgb", "Scaler", "frames_scale", "scale_table", "scale_taps", "Denoiser", "frames_denoise", "_lib"]

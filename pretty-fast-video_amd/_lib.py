@@ -195,6 +195,14 @@ SIGNATURES = [
     ("pfv_decoder_set_output_size", c_int, [_P, c_int, c_int, c_int]),
     ("pfv_enc_scale_dev", c_int, [_P, _P, _P, c_size_t, _P]),
     ("pfv_encoder_set_input_size", c_int, [_P, c_int, c_int, c_int]),
+    ("pfv_denoiser_create", _P, [_P, c_int, c_int, c_int, POINTER(c_int)]),
+    ("pfv_denoiser_destroy", None, [_P]),
+    ("pfv_denoiser_set_strength", c_int, [_P, _P, _P]),
+    ("pfv_denoiser_reset", c_int, [_P, c_int, c_int]),
+    ("pfv_denoiser_run_dev", c_int, [_P, c_int, c_int, _P, c_int, c_size_t, _P, c_size_t, c_int]),
+    ("pfv_frames_denoise", c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    ("pfv_enc_denoise_dev", c_int, [_P, _P, _P, c_size_t, c_int, _P]),
+    ("pfv_encoder_set_denoise", c_int, [_P, c_int, _P, _P]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),

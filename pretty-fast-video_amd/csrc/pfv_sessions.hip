@@ -103,6 +103,7 @@ struct pfv_enc_session {
     uint8_t *st_has = nullptr;
     uint8_t *ingest_frames = nullptr;        // packed frames of all slots made from RGB pictures (pfv_ingest.hip, pfv_enc_ingest_rgb_dev)
     uint8_t *scale_frames = nullptr;         // packed frames of all slots resized from frames of another size (pfv_scale.hip, pfv_enc_scale_dev)
+    uint8_t *denoise_frames = nullptr;       // packed frames of all slots behind the noise filter (pfv_denoise.hip, pfv_enc_denoise_dev)
     // distortion (pfv_quality.hip): the macroblock map when the caller passes none, the plane sums and where they land on the host
     uint32_t *q_map = nullptr;
     uint64_t *q_sse = nullptr;
@@ -266,7 +267,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->scale_frames, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->scale_frames, s->denoise_frames, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)

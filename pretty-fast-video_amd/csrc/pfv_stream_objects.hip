@@ -102,6 +102,12 @@ struct pfv_encoder {
     pfv_scaler *scaler = nullptr;          // src_w x src_h -> width x height; owned
     int src_w = 0, src_h = 0;
     uint8_t *scale_src = nullptr;          // device: the packed frame of the source size that waits for k_scale; made by the set call
+    // denoising pre-filter (pfv_encoder_set_denoise): the last input stage, between the stages above and the session's frame staging
+    bool dn_on = false;
+    pfv_denoiser *dn = nullptr;            // one stream of width x height; owned; made by the set call
+    uint8_t *dn_src = nullptr;             // device: the packed frame that waits for k_denoise; made by the set call
+    bool dn_commit = false;                // the entry point that is running commits (encode_*) or does not (probe_*)
+    bool dn_staged = false;                // ... and its filtered frame lies in the staging already: an upload is not repeated
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -665,7 +671,7 @@ static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const 
 {
     if (!planes_given(e, y, u, v)) return fail(e->ctx, PFV_ERR_BAD_ARG, e->rgb_on ? "RGB input is on: y is the picture, u and v must be NULL" : "null plane");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
-    if ((e->rgb_on || e->scaler) && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted / resized planes come back down
+    if ((e->rgb_on || e->scaler || e->dn_on) && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted / resized / filtered planes come back down
         pfv_ctx *ctx = e->ctx;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         int rc = enc_staging(e->hot);
@@ -711,10 +717,14 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
 {
     pfv_enc_session *s = e->hot;
     pfv_ctx *ctx = e->ctx;
-    // what the caller hands over has the size iw x ih; its planar form goes to `planar`: the staging itself, or where it waits for k_scale
+    // the filter's state moves once per frame: the entry point's first upload runs it, the frame then lies in the staging for the rest of the call
+    if (e->dn_on && e->dn_staged) return PFV_OK;
+    // what the caller hands over has the size iw x ih; its planar form goes to `planar`: the staging itself, or where it waits for k_scale or
+    // k_denoise; `sized`: where the frame of the session's size goes
     const int iw = e->scaler ? e->src_w : e->width, ih = e->scaler ? e->src_h : e->height;
-    const size_t ny = (size_t)iw * ih, nc = (size_t)(iw / 2) * (ih / 2);
-    uint8_t *planar = e->scaler ? e->scale_src : s->st_frames;
+    const size_t ny = (size_t)iw * ih, nc = (size_t)(iw / 2) * (ih / 2), fb = (size_t)s->geom.src_frame_bytes;
+    uint8_t *sized = e->dn_on ? e->dn_src : s->st_frames;
+    uint8_t *planar = e->scaler ? e->scale_src : sized;
     if (e->rgb_on) {   // the picture up into the encoder's scratch, one k_ingest_rgb
         const size_t row = pfv_rgb_row_bytes(iw, e->rgb_format);
         hipError_t he = hipMemcpyAsync(e->rgb_scratch, y, row * (size_t)ih, hipMemcpyHostToDevice, ctx->stream);
@@ -728,8 +738,14 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
         if (!packed && he == hipSuccess) he = hipMemcpyAsync(planar + ny + nc, v, nc, hipMemcpyHostToDevice, ctx->stream);
         if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(ctx, he, "plane upload"); }
     }
-    if (!e->scaler) return PFV_OK;
-    return scale_launch(e->scaler, 1, e->scale_src, PFV_FRAME_PACKED, ny + 2 * nc, s->st_frames, (size_t)s->geom.src_frame_bytes);   // one k_scale into the staging
+    if (e->scaler) {   // one k_scale into the staging, or to where the frame waits for k_denoise
+        const int rc = scale_launch(e->scaler, 1, e->scale_src, PFV_FRAME_PACKED, ny + 2 * nc, sized, fb);
+        if (rc) return rc;
+    }
+    if (!e->dn_on) return PFV_OK;
+    const int rc = denoise_launch(e->dn, 0, 1, e->dn_src, PFV_FRAME_PACKED, fb, s->st_frames, fb, e->dn_commit ? 1 : 0, "pfv_encoder");   // one k_denoise into the staging
+    if (!rc) e->dn_staged = true;
+    return rc;
 }
 
 // One frame through the device entropy stage: planes up (unless the i-frame budget's probe has put them there: `staged`), kernels, payload size
@@ -778,6 +794,7 @@ static int enc_input_scratch(pfv_encoder *e)
     pfv_ctx *ctx = e->ctx;
     const int iw = e->scaler ? e->src_w : e->width, ih = e->scaler ? e->src_h : e->height;
     if (e->scaler && !e->scale_src) HIP_TRY(ctx, hipMalloc((void **)&e->scale_src, pfv_frame_bytes(iw, ih)));
+    if (e->dn_on && !e->dn_src) HIP_TRY(ctx, hipMalloc((void **)&e->dn_src, pfv_frame_bytes(e->width, e->height)));
     const size_t pic = (size_t)iw * ih * 4;
     if (e->rgb_on && e->rgb_scratch_cap < pic) {
         if (e->rgb_scratch) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(e->rgb_scratch); e->rgb_scratch = nullptr; e->rgb_scratch_cap = 0; }
@@ -824,6 +841,28 @@ PFV_API int pfv_encoder_set_input_size(pfv_encoder *e, int src_w, int src_h, int
     if (e->scale_src) { (void)hipFree(e->scale_src); e->scale_src = nullptr; }
     e->scaler = sc;
     e->src_w = sc ? src_w : 0; e->src_h = sc ? src_h : 0;
+    return enc_input_scratch(e);
+}
+
+// Denoising pre-filter: while on, the frame of the session's size -- as handed over, converted or resized -- waits in scratch of the encoder and
+// one k_denoise puts it into the session's frame staging (upload_planes).  The encode_* calls commit, the probe_* calls do not.
+PFV_API int pfv_encoder_set_denoise(pfv_encoder *e, int on, const uint8_t spatial[3], const uint8_t temporal[3])
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!on) {
+        e->dn_on = false;
+        return PFV_OK;
+    }
+    pfv_ctx *ctx = e->ctx;
+    if (!spatial || !temporal) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_denoise: null strengths");
+    if (!denoise_strengths_ok(spatial, temporal)) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_denoise: strength above 16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = enc_staging(e->hot);
+    if (rc) return rc;
+    if (!e->dn && !(e->dn = pfv_denoiser_create(ctx, e->width, e->height, 1, &rc))) return rc;
+    if (!e->dn_on && (rc = pfv_denoiser_reset(e->dn, 0, 1))) return rc;   // switched on: the filter starts without a past
+    if ((rc = pfv_denoiser_set_strength(e->dn, spatial, temporal))) return rc;
+    e->dn_on = true;
     return enc_input_scratch(e);
 }
 
@@ -998,6 +1037,7 @@ PFV_API int pfv_encoder_encode_iframe(pfv_encoder *e, const uint8_t *y, const ui
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
+    e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     return write_iframe(e, y, u, v);
@@ -1008,6 +1048,7 @@ PFV_API int pfv_encoder_probe_iframe(pfv_encoder *e, const uint8_t *y, const uin
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!planes_given(e, y, u, v) || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
     if (!rc) rc = probe_staged(e->hot, sizes_out);
@@ -1019,6 +1060,7 @@ PFV_API int pfv_encoder_probe_iframe_rd(pfv_encoder *e, const uint8_t *y, const 
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!planes_given(e, y, u, v) || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_rd: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
     if (!rc) rc = rd_probe_staged(e->hot, sizes_out, sse_out);
@@ -1030,6 +1072,7 @@ PFV_API int pfv_encoder_probe_iframe_ssim(pfv_encoder *e, const uint8_t *y, cons
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!planes_given(e, y, u, v) || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_iframe_ssim: null buffer");
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
     if (!rc) rc = ssim_probe_staged(e->hot, false, sizes_out, sse_out, ssim_q24_out);
@@ -1053,6 +1096,7 @@ PFV_API int pfv_encoder_probe_pframe(pfv_encoder *e, const uint8_t *y, const uin
     if (!planes_given(e, y, u, v) || !sizes_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr);
 }
 // ... and its squared error per plane at every rung [n_rungs][3], from the same search and transform
@@ -1062,6 +1106,7 @@ PFV_API int pfv_encoder_probe_pframe_rd(pfv_encoder *e, const uint8_t *y, const 
     if (!planes_given(e, y, u, v) || !sizes_out || !sse_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_rd: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out);
 }
 // ... and its SSIM sums per plane at every rung [n_rungs][3]
@@ -1071,6 +1116,7 @@ PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, cons
     if (!planes_given(e, y, u, v) || !sizes_out || !sse_out || !ssim_q24_out) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_probe_pframe_ssim: null buffer");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
     if (e->poisoned) return fail(e->ctx, PFV_ERR_STATE, "the previous frame failed after prev_frame had advanced: encode an i-frame next");
+    e->dn_commit = false; e->dn_staged = false;   // a probe leaves the filter's state alone
     return probe_pframe_planes(e, y, u, v, sizes_out, nullptr, sse_out, ssim_q24_out);
 }
 PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
@@ -1133,6 +1179,7 @@ PFV_API int pfv_encoder_encode_pframe(pfv_encoder *e, const uint8_t *y, const ui
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
+    e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     // a previous frame failed after the encoder's reference had advanced but before its packet was written: a p-frame
@@ -1175,6 +1222,7 @@ PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uin
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
+    e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state
     int rc = pack_frame(e, y, u, v);
     if (rc) return rc;
     pfv_enc_session *s = e->hot;
@@ -1262,12 +1310,14 @@ PFV_API int pfv_encoder_drain(pfv_encoder *e, const uint8_t **data, size_t *len)
 PFV_API void pfv_encoder_destroy(pfv_encoder *e)
 {
     if (!e) return;
-    if (e->rgb_scratch || e->scaler) {
+    if (e->rgb_scratch || e->scaler || e->dn) {
         (void)hipSetDevice(e->ctx->device);
         (void)hipStreamSynchronize(e->ctx->stream);
         if (e->rgb_scratch) (void)hipFree(e->rgb_scratch);
         if (e->scale_src) (void)hipFree(e->scale_src);
+        if (e->dn_src) (void)hipFree(e->dn_src);
         pfv_scaler_destroy(e->scaler);
+        pfv_denoiser_destroy(e->dn);
     }
     pfv_enc_session_destroy(e->hot);
     delete e;

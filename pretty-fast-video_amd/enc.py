@@ -79,6 +79,13 @@ class Encoder:
         self._in_size = (int(src_width), int(src_height)) if src_width else None
         self._input_shapes()
 
+    def set_denoise(self, on=True, spatial=(0, 0, 0), temporal=(0, 0, 0)):
+        """the noise filter as the last input stage (behind set_input_rgb and set_input_size): strengths per plane (Y, U, V), 0 .. 16; the
+        encode_* methods commit the filter's state, the probe_* methods do not (pfv_encoder_set_denoise)"""
+        from .denoise import strengths
+        s, t = strengths(spatial), strengths(temporal)
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_denoise(self.handle, 1 if on else 0, ptr(s), ptr(t)))
+
     def _input_shapes(self):
         from .quality import rgb_shape
         w, h = getattr(self, "_in_size", None) or (self.width, self.height)

@@ -222,6 +222,15 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_scale_dev(self.handle, scaler.handle, ctypes.c_void_p(frames_dev), int(src_stride), ctypes.byref(out)))
         return int(out.value)
 
+    def denoise_dev(self, denoiser, frames_dev: int, src_stride: int = 0, commit: bool = True) -> int:
+        """asynchronous: the packed frames of the window's slots (slot k's at frames_dev + k * src_stride; 0: packed) through the noise filter
+        as the denoiser's streams k into slot k's frame of a packed buffer the session owns; returns that buffer's device address, a
+        `frames_dev` for the encode, probe, distortion_dev and ssim_dev calls (pfv_enc_denoise_dev)"""
+        out = ctypes.c_void_p()
+        self.ctx.check(self.ctx._lib.pfv_enc_denoise_dev(self.handle, denoiser.handle, ctypes.c_void_p(frames_dev), int(src_stride), 1 if commit else 0,
+                                                         ctypes.byref(out)))
+        return int(out.value)
+
     # GOP-batched use: the slots hold the GOPs of one stream (include/pfv_hip.h, pfv_enc_session_set_window) -----------
     def set_frame_stride(self, stride_bytes: int = 0):
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_frame_stride(self.handle, int(stride_bytes)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -22,6 +22,15 @@ what was measured as raw packed frames: q<quality>_input.yuv, q<quality>_recon.y
 --time-deblock (on the GPU box) adds one more line: k_deblock against k_crop_frames on the same 96 x 1080p launch -- pfv_dec_get_frame_dev of
 one decoder session with the switch fixed at (5, 10, 10), at (0, 0, 0) (the copy path) and off -- HIP events around every launch, warm-up, the
 median of the samples, alternating in three rounds; and pfv_dec_pframe_dev with an output buffer set, switch off (fused crop) against auto.
+
+--denoise SS,ST adds, per quality, what the denoising pre-filter (pfv_encoder_set_denoise, spatial strength SS and temporal ST on every plane)
+does to the clip PLUS seeded uniform noise in [-3, 3]: stream bytes and bytes per frame of the noisy clip without (noisy_*) and with the filter
+(dn_*), the PSNR of the encoder's input against the CLEAN clip (noisy_psnr_clean, dn_psnr_clean) and the share of p-frame macroblocks that are
+skipped (noisy_skipped_share, dn_skipped_share).  --dump DIR also writes q<quality>_clean.yuv, _noisy.yuv and _denoised.yuv.
+
+--time-denoise (on the GPU box) adds one more line: k_denoise (committed, steady state, strengths 6 / 6, packed and padded source) beside
+k_deblock and k_crop_frames on the same 96 x 1080p frames -- HIP events on the context's stream around every launch, warm-up, the median of
+the samples, alternating in three rounds.  With PFV_HIP_LIB set only one WIDTH x HEIGHT stream runs: the row is printed, its times mean nothing.
 
 --time-present (on the GPU box) adds six lines, one per pixel format (RGB8, RGBA8, BGRA8) on 96 x 1080p and on one WIDTH x HEIGHT stream: the
 RGB pictures of a decoder session's frames (a) by pfv_dec_get_frame_rgb_dev -- one k_present_rgb from the padded framebuffer; (b) the way without
@@ -298,6 +307,100 @@ def time_deblock(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30):
             "bytes_per_launch": bytes_moved, "deblock_GBps": bytes_moved / med["deblock"] / 1e6, "crop_GBps": bytes_moved / med["crop"] / 1e6,
             "dec_pframe_plus_output_off_ms": statistics.median(m for m, _, _ in loop["off"]),
             "dec_pframe_plus_output_auto_ms": statistics.median(m for m, _, _ in loop["auto"]), "dec_pframe_rounds_ms": loop}
+
+
+def noisy_clip(pkg, w, h, n_frames, kind, seed=2024):
+    """the synthetic clip and the same clip with seeded uniform noise in [-3, 3], clipped"""
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    clean = np.stack([st.frame(t) for t in range(n_frames)])
+    rng = np.random.default_rng(seed)
+    return clean, np.clip(clean.astype(np.int64) + rng.integers(-3, 4, clean.shape), 0, 255).astype(np.uint8)
+
+
+def denoise_line(pkg, ctx, w, h, n_frames, gop, kind, quality, ss, st, dump=None):
+    """the keys --denoise adds to a quality's line: the NOISY clip encoded without and with the pre-filter (pfv_encoder_set_denoise)"""
+    clean, noisy = noisy_clip(pkg, w, h, n_frames, kind)
+    spatial, temporal = (ss,) * 3, (st,) * 3
+    filt = pkg.frames_denoise(ctx, w, h, noisy, spatial, temporal)
+    out = {"dn_strength": [ss, st]}
+    for key, on in (("noisy", False), ("dn", True)):
+        buf = io.BytesIO()
+        enc = pkg.Encoder(buf, w, h, 30, quality, ctx)
+        sess = pkg.EncoderSession(ctx, w, h, quality, 1)
+        if on:
+            enc.set_denoise(True, spatial, temporal)
+        skipped = total = 0
+        for t in range(n_frames):
+            (enc.encode_iframe if t % gop == 0 else enc.encode_pframe)(pkg.VideoFrame.from_packed(w, h, noisy[t]))
+            f = filt[t] if on else noisy[t]
+            if t % gop == 0:
+                sess.encode_iframe(f)
+            else:
+                _, has, _ = sess.encode_pframe(f)
+                skipped, total = skipped + int((has == 0).sum()), total + int(has.size)
+        enc.finish()
+        enc.close()
+        sess.close()
+        d = (clean.astype(np.int64) - (filt if on else noisy)) ** 2
+        out.update({f"{key}_stream_bytes": len(buf.getvalue()), f"{key}_bytes_per_frame": len(buf.getvalue()) / n_frames,
+                    f"{key}_psnr_clean": pkg.psnr(int(d.sum()), d.size), f"{key}_skipped": skipped, f"{key}_skipped_share": skipped / total if total else None})
+    out["pframe_macroblocks"] = total
+    if dump:
+        os.makedirs(dump, exist_ok=True)
+        for name, arr in (("clean", clean), ("noisy", noisy), ("denoised", filt)):
+            arr.tofile(os.path.join(dump, f"q{quality}_{name}.yuv"))
+    return out
+
+
+def time_denoise(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
+    """k_denoise (committed, strengths 6 / 6, packed and padded source) beside k_deblock (padded source, strengths 5 / 10 / 10) and k_crop_frames
+    on the same frames: medians of HIP-event times on the context's stream, the kernels alternating in every round"""
+    lib = ctx._lib
+    P = ctypes.c_void_p
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    f0, out = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef = ctx.alloc(n_streams * tb * 512)
+    ctx.synth_frames_dev(w, h, np.arange(1, n_streams + 1, dtype=np.uint64), 0, f0)
+    enc = pkg.EncoderSession(ctx, w, h, 10, n_streams)
+    dec = pkg.DecoderSession(ctx, w, h, np.stack(pkg.qtables_from_quality(10)[:4]), n_streams)
+    enc.encode_iframe_dev(f0, coef)
+    dec.decode_iframe_dev(coef)
+    prev = lib.pfv_enc_prev_frame_dev(enc.handle, 0)          # the same frames, padded
+    dn = pkg.Denoiser(ctx, w, h, n_streams, (6, 6, 6), (6, 6, 6))
+    dn.run_dev(f0, out)                                        # primes: the timed runs are the steady state, one kernel each
+    st = np.array([5, 10, 10], np.uint8)
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn):
+        got = []
+        for k in range(warmup + samples):
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got)
+    dec.set_deblock("off")
+    cases = {"denoise_packed": lambda: dn.run_dev(f0, out), "denoise_padded": lambda: dn.run_dev(prev, out, src_layout="padded"),
+             "deblock": lambda: ctx.check(lib.pfv_frames_deblock_dev(ctx.handle, w, h, n_streams, P(prev), pkg._lib.PFV_FRAME_PADDED, 0, P(out), 0, st.ctypes.data_as(P))),
+             "crop": lambda: dec.get_frame_dev(out)}
+    res = {k: [] for k in cases}
+    for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
+        for key, fn in cases.items():
+            res[key].append(median_ms(fn))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    dn.close(); enc.close(); dec.close()
+    for p in (f0, out, coef):
+        ctx.free(p)
+    med = {k: statistics.median(v) for k, v in res.items()}
+    pfb = int(lib.pfv_padded_frame_bytes(w, h))
+    moved = {"denoise_packed": n_streams * 4 * fb, "denoise_padded": n_streams * (pfb + 3 * fb), "deblock": n_streams * (pfb + fb), "crop": n_streams * (pfb + fb)}
+    return {"shape": f"{n_streams} x {w}x{h}", "samples_per_round": samples, "rounds": rounds, **{f"{k}_ms": v for k, v in med.items()},
+            **{f"{k}_GBps": moved[k] / med[k] / 1e6 if med[k] else None for k in med}, "rounds_ms": res}
 
 
 def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
@@ -1103,6 +1206,8 @@ def main():
     ap.add_argument("--time-present", action="store_true")
     ap.add_argument("--time-ingest", action="store_true")
     ap.add_argument("--time-scale", action="store_true")
+    ap.add_argument("--denoise", default=None, metavar="SS,ST")
+    ap.add_argument("--time-denoise", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -1111,11 +1216,18 @@ def main():
             line = rd_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, with_ssim=a.ssim)
             if a.deblock:
                 line.update(deblock_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, dump=a.dump))
+            if a.denoise:
+                ss, st = (int(x) for x in a.denoise.split(","))
+                line.update(denoise_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, ss, st, dump=a.dump))
             print(json.dumps(line), flush=True)
         if a.time_ssim:
             print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
         if a.time_deblock:
             print(json.dumps({"time_deblock": time_deblock(pkg, ctx)}), flush=True)
+        if a.time_denoise:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the row only
+            kw = dict(n_streams=1, w=a.width, h=a.height, warmup=1, samples=2, rounds=1) if emu else {}
+            print(json.dumps({"time_denoise": time_denoise(pkg, ctx, **kw)}), flush=True)
         if a.time_present:
             emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the rows only
             for shape in ([] if emu else [dict(n_streams=96, w=1920, h=1080)]) + [dict(n_streams=1, w=a.width, h=a.height)]:
