@@ -254,6 +254,65 @@ inline std::vector<uint8_t> frames_denoise(Context &ctx, size_t width, size_t he
     return out;
 }
 
+// motion search of an encoder session and of the stream encoders over it (pfv_*_set_motion_search): FourStep is the reference's search
+enum class MotionSearch { FourStep = PFV_SEARCH_FOURSTEP, Full = PFV_SEARCH_FULL };
+
+// The hot-path half of enc::Encoder for n streams (pfv_enc_session): packed frames of all streams in, the macroblock arrays out.
+class EncoderSession {
+  public:
+    EncoderSession(Context &ctx, size_t width, size_t height, int quality, int n_streams = 1) : ctx_(ctx), n_(n_streams)
+    {
+        ctx_.check(pfv_enc_session_create(ctx.handle(), (int)width, (int)height, quality, n_streams, &h_));
+        blocks_ = (size_t)pfv_total_blocks((int)width, (int)height);
+        frame_bytes_ = pfv_frame_bytes((int)width, (int)height);
+    }
+    ~EncoderSession() { pfv_enc_session_destroy(h_); }
+    EncoderSession(const EncoderSession &) = delete;
+    EncoderSession &operator=(const EncoderSession &) = delete;
+    pfv_enc_session *handle() const { return h_; }
+    size_t total_blocks() const { return blocks_; }
+    // the search of the p-frame launches that follow; radius 1 .. 15 for Full, ignored for FourStep
+    void set_motion_search(MotionSearch mode, int radius = 0) { ctx_.check(pfv_enc_session_set_motion_search(h_, (int)mode, radius)); }
+    std::pair<MotionSearch, int> motion_search() const
+    {
+        int m = 0, r = 0;
+        ctx_.check(pfv_enc_session_get_motion_search(h_, &m, &r));
+        return {(MotionSearch)m, r};
+    }
+    struct PFrame {
+        std::vector<int8_t> mv;          // [stream][macroblock][2]
+        std::vector<uint8_t> has_coef;   // [stream][macroblock]
+        std::vector<int16_t> coef;       // [stream][macroblock][256]
+    };
+    std::vector<int16_t> encode_iframe(const std::vector<uint8_t> &frames)
+    {
+        check_frames(frames);
+        std::vector<int16_t> coef(blocks_ * (size_t)n_ * 256);
+        ctx_.check(pfv_enc_iframe(h_, frames.data(), coef.data()));
+        return coef;
+    }
+    PFrame encode_pframe(const std::vector<uint8_t> &frames)
+    {
+        check_frames(frames);
+        PFrame p;
+        p.mv.resize(blocks_ * (size_t)n_ * 2);
+        p.has_coef.resize(blocks_ * (size_t)n_);
+        p.coef.resize(blocks_ * (size_t)n_ * 256);
+        ctx_.check(pfv_enc_pframe(h_, frames.data(), p.mv.data(), p.has_coef.data(), p.coef.data()));
+        return p;
+    }
+
+  private:
+    void check_frames(const std::vector<uint8_t> &frames) const
+    {
+        if (frames.size() != frame_bytes_ * (size_t)n_) throw std::invalid_argument("EncoderSession: frames must hold one packed frame per stream");
+    }
+    Context &ctx_;
+    int n_;
+    size_t blocks_ = 0, frame_bytes_ = 0;
+    pfv_enc_session *h_ = nullptr;
+};
+
 class Encoder {
   public:
     Encoder(std::ostream &writer, size_t width, size_t height, uint32_t framerate, int quality, Context &ctx)
@@ -354,6 +413,8 @@ class Encoder {
     void set_frame_ssim(bool on) { ctx_.check(pfv_encoder_set_frame_ssim(h_, on ? 1 : 0)); }
     // quality ladder: the rung of the frames that follow / of the last frame written (before the first frame: the current rung)
     void set_rung(int rung) { ctx_.check(pfv_encoder_set_rung(h_, rung)); }
+    // the search of the p-frames that follow; Full excludes the p-frame probe, the p-frame floors and encode_frame
+    void set_motion_search(MotionSearch mode, int radius = 0) { ctx_.check(pfv_encoder_set_motion_search(h_, (int)mode, radius)); }
     int rung() const { return pfv_encoder_rung(h_); }
     int n_rungs() const { return pfv_encoder_rungs(h_); }
     // byte budget per p-frame payload, 0 = off (pfv_encoder_set_rate)
@@ -634,6 +695,8 @@ class GopEncoder {
     // device frames are read where they lie instead of being copied into the batch; the caller keeps each one valid and unchanged until its
     // packet has reached the writer (or flush() / finish() returned)
     void set_frames_by_reference(bool on) { ctx_.check(pfv_gop_encoder_set_frames_by_reference(h_, on ? 1 : 0)); }
+    // the search of the batches submitted from now on; throws (PFV_ERR_STATE) while a batch is in flight
+    void set_motion_search(MotionSearch mode, int radius = 0) { ctx_.check(pfv_gop_encoder_set_motion_search(h_, (int)mode, radius)); }
     // a packed frame (Y | U | V) that already lies in device memory: nothing crosses PCIe on the way in.  Stream-ordered on the context's
     // stream like every *_dev call: no host wait, the frame may only be overwritten by work enqueued on that stream afterwards
     void encode_iframe_device(const uint8_t *frame_dev)

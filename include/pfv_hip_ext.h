@@ -653,6 +653,42 @@ PFV_API int pfv_enc_denoise_dev(pfv_enc_session *s, pfv_denoiser *dn, const uint
  * it is without the switch. */
 PFV_API int pfv_encoder_set_denoise(pfv_encoder *e, int on, const uint8_t spatial[3], const uint8_t temporal[3]);
 
+/* ------------------------------------------------------------------ exhaustive motion search  [B]
+ * The reference chooses a macroblock's vector with a four-step logarithmic search (src/common.rs:154-204: steps 8, 4, 2, 1, 33 candidates), which
+ * walks down one slope of the error surface and stops in a local minimum on textured content or large motion.  PFV_SEARCH_FULL looks at every
+ * vector instead.  It is a MODE of an encoder session, not a PFV_OPT_*: its streams are ordinary .pfv streams that every decoder takes, but they
+ * are not the reference encoder's bytes.  Default PFV_SEARCH_FOURSTEP: no launch and no byte differs from a session without this call.
+ *
+ * The rule (normative), for the macroblock at origin (bx, by) of a plane padded to pw x ph, against the session's previous reconstruction, with
+ * radius R in 1 .. 15:
+ *   candidates   all (dx, dy) with |dx| <= R, |dy| <= R, 0 <= bx + dx <= pw - 16, 0 <= by + dy <= ph - 16 (the bounds of src/common.rs:171, :182);
+ *   E(dx, dy)    the exact integer sum of squared differences over the 16 x 16 block, at most 256 * 255^2 < 2^24: equal to the f32 value the
+ *                reference compares;
+ *   chosen       the lexicographic minimum of (E, |dx| + |dy|, dy, dx): (0, 0) wins every tie it takes part in, among equal errors the
+ *                shortest vector wins, then the smallest dy, then the smallest dx.
+ * Everything behind the choice is the existing operator: has_coef = !((float)E <= px_err^2 * 256) at the launch's rung; a skipped macroblock
+ * has zero coefficients and the patch as its reconstruction; a coded one is clip(src - patch, +-255) -> encode_subblock_delta -> closed-loop
+ * decode_block_delta.
+ * Two launches: k_pf_search_full (csrc/pfv_fullsearch_kernels.hip) and k_pf_transform on the coded macroblocks.  One lane mapping at every grid
+ * size: PFV_OPT_LANE_MAPPING and PFV_OPT_TILE_COMPACTION do not apply, PFV_OPT_ENC_TRANSFORM still selects the transform's form.  The outputs have
+ * the four-step launch's layout, so rungs, windows, frame strides, by-reference slots, the ingest / scale / denoise stages, the device entropy
+ * stage and the distortion / SSIM reports work unchanged.  Cost: profiles/full_search.md.
+ * The mode applies to the p-frame launches that follow, like pfv_enc_session_set_rung; a launch recorded in a graph keeps the mode at capture
+ * time.  radius: 1 .. 15 for FULL, ignored for FOURSTEP (reads back as 0).  An unknown mode or a radius outside 1 .. 15: PFV_ERR_BAD_ARG, and the
+ * mode stays as it was.
+ * The p-frame probes restate the four-step front end: while a session is in FULL mode pfv_enc_probe_pframe{,_rd,_ssim}{,_dev} return
+ * PFV_ERR_STATE (so do pfv_encoder_probe_pframe*).  pfv_encoder_set_motion_search(FULL) is refused with PFV_ERR_STATE while
+ * pfv_encoder_set_pframe_probe, pfv_encoder_set_pframe_quality_floor or pfv_encoder_set_pframe_ssim_floor is on, switching one of those on is
+ * refused while FULL is on, and pfv_encoder_encode_frame returns PFV_ERR_STATE in FULL mode.  pfv_encoder_set_rate, the rungs and the i-frame
+ * probes, budget and floors are unaffected.  pfv_gop_encoder: a batch that is made again (arena outgrown) takes the encoder's mode;
+ * a change while a batch is in flight is refused with PFV_ERR_STATE (pfv_gop_encoder_flush first).  pfv_batch_encoder and the plane operator
+ * pfv_encode_plane_delta have no switch. */
+enum { PFV_SEARCH_FOURSTEP = 0, PFV_SEARCH_FULL = 1 };
+PFV_API int pfv_enc_session_set_motion_search(pfv_enc_session *s, int mode, int radius);
+PFV_API int pfv_enc_session_get_motion_search(pfv_enc_session *s, int *mode, int *radius);   /* either pointer may be NULL */
+PFV_API int pfv_encoder_set_motion_search(pfv_encoder *e, int mode, int radius);
+/* pfv_gop_encoder_set_motion_search: with the GOP encoder below */
+
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the
  * reference's encoder writes four tables and one quality for the whole stream.  A LADDER is several qualities in one stream: `qualities`
@@ -933,6 +969,8 @@ PFV_API int pfv_gop_encoder_encode_pframe_dev(pfv_gop_encoder *e, const uint8_t 
  * _finish has returned.  Same bytes.  (The frame-at-a-time contract of Encoder::encode_pframe, src/enc.rs:125 -- the frame is borrowed for
  * the call only -- is what forces the copy by default; a renderer that keeps a ring of frames does not need it.) */
 PFV_API int pfv_gop_encoder_set_frames_by_reference(pfv_gop_encoder *e, int on);
+/* the motion search of the batches submitted from now on ("exhaustive motion search" above); PFV_ERR_STATE while a batch is in flight */
+PFV_API int pfv_gop_encoder_set_motion_search(pfv_gop_encoder *e, int mode, int radius);
 PFV_API int pfv_gop_encoder_encode_dropframe(pfv_gop_encoder *e);
 PFV_API int pfv_gop_encoder_flush(pfv_gop_encoder *e);
 PFV_API int pfv_gop_encoder_finish(pfv_gop_encoder *e);

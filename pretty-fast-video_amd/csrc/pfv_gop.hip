@@ -271,6 +271,7 @@ static int gop_enc_redo(pfv_gop_encoder *e, GopEncBatch &B)
     pfv_enc_session *r = nullptr;
     int rc = pfv_enc_session_create(ctx, e->width, e->height, e->quality, 1, &r);
     if (!rc) rc = pfv_enc_entropy_enable(r, 0);
+    if (!rc) rc = pfv_enc_session_set_motion_search(r, e->hot->search_mode, e->hot->search_radius);   // the batch's own search: same bytes
     B.redo.clear();
     e->redo_sizes.clear();
     const size_t pad = (size_t)e->hot->geom.pad_frame_bytes;
@@ -604,6 +605,14 @@ PFV_API int pfv_gop_encoder_set_frames_by_reference(pfv_gop_encoder *e, int on)
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     e->frames_by_ref = on != 0;
     return PFV_OK;
+}
+// The motion search of the batches submitted from now on (the hot session's mode; a batch made again takes it too).  Refused while a batch is
+// in flight: its frames were searched one way and would be made again the other.
+PFV_API int pfv_gop_encoder_set_motion_search(pfv_gop_encoder *e, int mode, int radius)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->batch[0].in_flight || e->batch[1].in_flight) return fail(e->ctx, PFV_ERR_STATE, "pfv_gop_encoder_set_motion_search: a batch is in flight (pfv_gop_encoder_flush first)");
+    return pfv_enc_session_set_motion_search(e->hot, mode, radius);
 }
 PFV_API int pfv_gop_encoder_encode_iframe_dev(pfv_gop_encoder *e, const uint8_t *frame_dev) { return gop_enc_frame_dev(e, 1, frame_dev); }
 PFV_API int pfv_gop_encoder_encode_pframe_dev(pfv_gop_encoder *e, const uint8_t *frame_dev) { return gop_enc_frame_dev(e, 2, frame_dev); }

@@ -159,6 +159,16 @@ static void launch_enc_pframe(pfv_ctx *ctx, bool flt, bool small, int compaction
         else hipLaunchKernelGGL(k_pf_transform<false>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
     }
 }
+// PFV_SEARCH_FULL (pfv_fullsearch_kernels.hip): the exhaustive search, then the split form's transform kernel on the coded macroblocks.  One
+// mapping at every grid size: PFV_OPT_LANE_MAPPING and PFV_OPT_TILE_COMPACTION do not apply.
+static void launch_enc_pframe_full(pfv_ctx *ctx, bool flt, int radius, const FrameGeom &g, const uint8_t *src, const uint8_t *ref, int8_t *mv, uint8_t *has,
+                                   int16_t *coef, uint8_t *recon, const QTab *qt, float min_err)
+{
+    hipLaunchKernelGGL(k_pf_search_full, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, src, ref, mv, has, coef, recon, min_err, radius);
+    const unsigned tf = (unsigned)((long)g.n_streams * tf_groups_per_frame(g));
+    if (flt) hipLaunchKernelGGL(k_pf_transform<true>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
+    else hipLaunchKernelGGL(k_pf_transform<false>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
+}
 // where a decode launch finds its coefficients: the dense [slot][macroblock][256] array, or coefficient lists (pfv_device.h: CoefLists)
 struct DecCoefs {
     const int16_t *dense = nullptr;

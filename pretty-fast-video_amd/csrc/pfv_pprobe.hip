@@ -59,11 +59,13 @@ extern "C" {
 
 PFV_API int pfv_enc_probe_pframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint32_t *stats_dev)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe_dev")) return rf;
     int rc = probe_dev_enter(s, frames_dev && sizes_dev, "pfv_enc_probe_pframe_dev");
     return rc ? rc : pprobe_launch(s, frames_dev, sizes_dev, stats_dev);
 }
 PFV_API int pfv_enc_probe_pframe(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe")) return rf;
     int rc = probe_host_enter(s, frames, sizes_out != nullptr, "pfv_enc_probe_pframe");
     return rc ? rc : pprobe_staged(s, sizes_out);
 }

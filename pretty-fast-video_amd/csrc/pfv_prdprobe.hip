@@ -48,11 +48,13 @@ extern "C" {
 
 PFV_API int pfv_enc_probe_pframe_rd_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, uint32_t *stats_dev)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe_rd_dev")) return rf;
     int rc = probe_dev_enter(s, frames_dev && sizes_dev && sse_dev, "pfv_enc_probe_pframe_rd_dev");
     return rc ? rc : prd_probe_launch(s, frames_dev, sizes_dev, sse_dev, stats_dev);
 }
 PFV_API int pfv_enc_probe_pframe_rd(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe_rd")) return rf;
     int rc = probe_host_enter(s, frames, sizes_out && sse_out, "pfv_enc_probe_pframe_rd");
     return rc ? rc : prd_probe_staged(s, sizes_out, sse_out);
 }

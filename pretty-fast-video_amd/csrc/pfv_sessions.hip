@@ -92,6 +92,8 @@ struct pfv_enc_session {
     bool flt = false;                        // the closed loop may run in f32 (enc_float_exact holds for all tables of all rungs)
     int tile_compaction = 1;                 // PFV_OPT_TILE_COMPACTION at creation
     int lane_mapping = PFV_LANES_AUTO;       // PFV_OPT_LANE_MAPPING at creation
+    int search_mode = PFV_SEARCH_FOURSTEP;   // pfv_enc_session_set_motion_search: applies to the p-frame launches that follow
+    int search_radius = 0;                   // PFV_SEARCH_FULL: 1..15
     uint8_t *prev[2] = {nullptr, nullptr};   // ping-pong prev_frame, padded, n_streams wide
     int cur = 0;                             // prev[cur] is the current prev_frame
     int win_first = 0, win_count = 0;        // slot window of the *_dev / pack calls (pfv_enc_session_set_window)
@@ -260,6 +262,29 @@ PFV_API int pfv_enc_session_set_rung(pfv_enc_session *s, int rung)
     return PFV_OK;
 }
 PFV_API int pfv_enc_session_rung(pfv_enc_session *s) { return s ? s->rung : PFV_ERR_BAD_ARG; }
+// how the p-frame launches that follow choose their motion vectors; the rule of PFV_SEARCH_FULL is at the declaration (include/pfv_hip_ext.h)
+PFV_API int pfv_enc_session_set_motion_search(pfv_enc_session *s, int mode, int radius)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    if (mode != PFV_SEARCH_FOURSTEP && mode != PFV_SEARCH_FULL) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: unknown mode");
+    if (mode == PFV_SEARCH_FULL && (radius < 1 || radius > 15)) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: the radius of the full search is 1..15");
+    s->search_mode = mode;
+    s->search_radius = mode == PFV_SEARCH_FULL ? radius : 0;
+    return PFV_OK;
+}
+PFV_API int pfv_enc_session_get_motion_search(pfv_enc_session *s, int *mode, int *radius)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    if (mode) *mode = s->search_mode;
+    if (radius) *radius = s->search_radius;
+    return PFV_OK;
+}
+// the p-frame probes restate the four-step front end (probe_tile_front): under the full search they would size another encoder's frames
+static int enc_pframe_probe_refused(pfv_enc_session *s, const char *who)
+{
+    if (s && s->search_mode == PFV_SEARCH_FULL) return fail(s->ctx, PFV_ERR_STATE, std::string(who) + ": the p-frame probes follow the four-step search; the session is in PFV_SEARCH_FULL");
+    return PFV_OK;
+}
 PFV_API int pfv_enc_session_rungs(pfv_enc_session *s) { return s ? s->n_rungs : PFV_ERR_BAD_ARG; }
 
 PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
@@ -313,6 +338,11 @@ static int enc_launch(pfv_enc_session *s, bool pframe, int first, int count, con
     const QTab *rung_tabs = s->qtab_dev + 4 * s->rung;           // the rung of this launch: its four tables, its px_err
     if (pframe) {
         const float min_err = s->px_err[s->rung] * s->px_err[s->rung] * 256.0f;   // src/common.rs:209
+        if (s->search_mode == PFV_SEARCH_FULL) {
+            launch_enc_pframe_full(ctx, s->flt, s->search_radius, g, src, s->prev[s->cur] + pad0, mv_dev + mb0 * 2, has_dev + mb0, coef_dev + mb0 * 256,
+                                   s->prev[nxt] + pad0, rung_tabs + 2, min_err);
+            return launch_check(ctx, "k_pf_search_full");
+        }
         launch_enc_pframe(ctx, s->flt, use_small_grid(s->lane_mapping, g), s->tile_compaction, g, src, s->prev[s->cur] + pad0, mv_dev + mb0 * 2,
                           has_dev + mb0, coef_dev + mb0 * 256, s->prev[nxt] + pad0, rung_tabs + 2, min_err);
         return launch_check(ctx, "k_enc_pframe");

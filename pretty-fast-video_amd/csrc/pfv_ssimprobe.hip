@@ -80,11 +80,13 @@ PFV_API int pfv_enc_probe_iframe_ssim(pfv_enc_session *s, const uint8_t *frames,
 }
 PFV_API int pfv_enc_probe_pframe_ssim_dev(pfv_enc_session *s, const uint8_t *frames_dev, uint32_t *sizes_dev, uint64_t *sse_dev, int64_t *ssim_q24_dev, uint32_t *stats_dev)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe_ssim_dev")) return rf;
     int rc = probe_dev_enter(s, frames_dev && sizes_dev && sse_dev && ssim_q24_dev, "pfv_enc_probe_pframe_ssim_dev");
     return rc ? rc : ssim_probe_launch(s, true, frames_dev, sizes_dev, sse_dev, ssim_q24_dev, stats_dev);
 }
 PFV_API int pfv_enc_probe_pframe_ssim(pfv_enc_session *s, const uint8_t *frames, uint32_t *sizes_out, uint64_t *sse_out, int64_t *ssim_q24_out)
 {
+    if (int rf = enc_pframe_probe_refused(s, "pfv_enc_probe_pframe_ssim")) return rf;
     int rc = probe_host_enter(s, frames, sizes_out && sse_out && ssim_q24_out, "pfv_enc_probe_pframe_ssim");
     return rc ? rc : ssim_probe_staged(s, true, sizes_out, sse_out, ssim_q24_out);
 }

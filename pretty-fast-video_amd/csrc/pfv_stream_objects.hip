@@ -605,6 +605,7 @@ PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!(min_psnr_yuv >= 0.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_quality_floor: the floor must be >= 0 dB (+INFINITY is legal, NaN is not)");
+    if (min_psnr_yuv > 0.0 && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_quality_floor: the p-frame probes do not follow PFV_SEARCH_FULL");
     e->floor_p = min_psnr_yuv;
     return PFV_OK;
 }
@@ -621,6 +622,7 @@ PFV_API int pfv_encoder_set_pframe_ssim_floor(pfv_encoder *e, double min_ssim)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!(min_ssim >= 0.0 && min_ssim <= 1.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_ssim_floor: the floor must lie in [0, 1] (NaN is not legal)");
+    if (min_ssim > 0.0 && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_ssim_floor: the p-frame probes do not follow PFV_SEARCH_FULL");
     e->sfloor_p = min_ssim;
     return PFV_OK;
 }
@@ -1083,6 +1085,7 @@ PFV_API int pfv_encoder_probe_iframe_ssim(pfv_encoder *e, const uint8_t *y, cons
 static int probe_pframe_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint32_t *sizes, uint32_t *counts, uint64_t *sse = nullptr,
                                int64_t *q24 = nullptr)
 {
+    if (int rf = enc_pframe_probe_refused(e->hot, "pfv_encoder_probe_pframe")) return rf;
     HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
     int rc = enc_staging(e->hot);
     if (!rc) rc = upload_planes(e, y, u, v);
@@ -1122,8 +1125,17 @@ PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, cons
 PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (on && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_probe: the p-frame probes do not follow PFV_SEARCH_FULL");
     e->pprobe_on = on != 0;
     return PFV_OK;
+}
+// the motion search of the p-frames that follow (the hot session's mode); refused while anything that probes p-frames is on
+PFV_API int pfv_encoder_set_motion_search(pfv_encoder *e, int mode, int radius)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (mode == PFV_SEARCH_FULL && radius >= 1 && radius <= 15 && (e->pprobe_on || e->floor_p > 0.0 || e->sfloor_p > 0.0))
+        return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_motion_search: the p-frame probe and the p-frame floors do not follow PFV_SEARCH_FULL: switch them off first");
+    return pfv_enc_session_set_motion_search(e->hot, mode, radius);
 }
 PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval)
 {
@@ -1220,6 +1232,7 @@ static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint6
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_encode_frame: the frame type comes from the p-frame probes, which do not follow PFV_SEARCH_FULL");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
     e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state

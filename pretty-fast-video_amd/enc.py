@@ -86,6 +86,12 @@ class Encoder:
         s, t = strengths(spatial), strengths(temporal)
         self.ctx.check(self.ctx._lib.pfv_encoder_set_denoise(self.handle, 1 if on else 0, ptr(s), ptr(t)))
 
+    def set_motion_search(self, mode="fourstep", radius: int = 0):
+        """the motion search of the p-frames that follow: "fourstep" or "full" with a radius of 1..15 (pfv_encoder_set_motion_search);
+        full mode excludes the p-frame probe, the p-frame floors and encode_frame"""
+        from ._lib import search_mode
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_motion_search(self.handle, search_mode(mode), int(radius)))
+
     def _input_shapes(self):
         from .quality import rgb_shape
         w, h = getattr(self, "_in_size", None) or (self.width, self.height)
@@ -435,6 +441,12 @@ class GopEncoder(Encoder):
     def encode_pframe(self, frame):
         self.ctx.check(self.ctx._lib.pfv_gop_encoder_encode_pframe(self.handle, *self._planes(frame)))
         self._flush()
+
+    def set_motion_search(self, mode="fourstep", radius: int = 0):
+        """the motion search of the batches submitted from now on: "fourstep" or "full" with a radius of 1..15; refused while a batch is
+        in flight (pfv_gop_encoder_set_motion_search)"""
+        from ._lib import search_mode
+        self.ctx.check(self.ctx._lib.pfv_gop_encoder_set_motion_search(self.handle, search_mode(mode), int(radius)))
 
     def set_frames_by_reference(self, on: bool = True):
         """device frames (encode_*_dev) are read where they lie instead of being copied into the batch: the caller keeps each frame valid and

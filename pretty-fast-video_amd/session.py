@@ -73,6 +73,20 @@ class EncoderSession(_Geometry):
         """the rung of the encode / pack launches that follow (all slots of a launch share it)"""
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_rung(self.handle, int(rung)))
 
+    # motion search ------------------------------------------------------
+    def set_motion_search(self, mode="fourstep", radius: int = 0):
+        """how the p-frame launches that follow choose their vectors: "fourstep" (the reference's search, the default) or "full" with a
+        radius of 1..15, every vector of the square (pfv_enc_session_set_motion_search); the p-frame probes are refused in full mode"""
+        from ._lib import search_mode
+        self.ctx.check(self.ctx._lib.pfv_enc_session_set_motion_search(self.handle, search_mode(mode), int(radius)))
+
+    @property
+    def motion_search(self):
+        """(mode, radius): PFV_SEARCH_FOURSTEP / PFV_SEARCH_FULL, and the radius (0 for four-step)"""
+        m, r = ctypes.c_int(), ctypes.c_int()
+        self.ctx.check(self.ctx._lib.pfv_enc_session_get_motion_search(self.handle, ctypes.byref(m), ctypes.byref(r)))
+        return int(m.value), int(r.value)
+
     # i-frame size probe -------------------------------------------------
     def probe_iframe(self, frames) -> np.ndarray:
         """payload bytes of every stream's frame as an i-frame at every rung, uint32 [n_streams, n_rungs], from one read of the frames

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise] [--search full[,R]] [--time-search]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -31,6 +31,16 @@ skipped (noisy_skipped_share, dn_skipped_share).  --dump DIR also writes q<quali
 --time-denoise (on the GPU box) adds one more line: k_denoise (committed, steady state, strengths 6 / 6, packed and padded source) beside
 k_deblock and k_crop_frames on the same 96 x 1080p frames -- HIP events on the context's stream around every launch, warm-up, the median of
 the samples, alternating in three rounds.  With PFV_HIP_LIB set only one WIDTH x HEIGHT stream runs: the row is printed, its times mean nothing.
+
+--search full[,R] (R = 1 .. 15, default 15) adds, per quality, the clip encoded with both motion searches (pfv_encoder_set_motion_search) side by
+side: four_ / full_ stream_bytes, psnr_yuv (mean over the frames, frame reports), and the coded and skipped p-frame macroblocks (an encoder
+session fed the same frames); search_radius = R.
+
+--time-search (on the GPU box) adds one more line: k_pf_search_full + k_pf_transform at R = 7 and R = 15 against the default p-frame encode of
+the same 96 x 1080p frames (frame 1 of the synthetic streams behind frame 0 as an i-frame) -- HIP events on the context's stream around every
+pfv_enc_pframe_dev, warm-up, the median of the samples, the three alternating in three rounds; the ratios to the default encode and to the
+v_dot4 issue floor of the products alone ((2R + 1)^2 x 64 per macroblock over its 8 lanes, 4.2 cycles each, 1 024 SIMDs, 2.4 GHz).  With PFV_HIP_LIB set only two
+WIDTH x HEIGHT streams run: the row is printed, its times mean nothing.
 
 --time-present (on the GPU box) adds six lines, one per pixel format (RGB8, RGBA8, BGRA8) on 96 x 1080p and on one WIDTH x HEIGHT stream: the
 RGB pictures of a decoder session's frames (a) by pfv_dec_get_frame_rgb_dev -- one k_present_rgb from the padded framebuffer; (b) the way without
@@ -401,6 +411,86 @@ def time_denoise(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30, r
     moved = {"denoise_packed": n_streams * 4 * fb, "denoise_padded": n_streams * (pfb + 3 * fb), "deblock": n_streams * (pfb + fb), "crop": n_streams * (pfb + fb)}
     return {"shape": f"{n_streams} x {w}x{h}", "samples_per_round": samples, "rounds": rounds, **{f"{k}_ms": v for k, v in med.items()},
             **{f"{k}_GBps": moved[k] / med[k] / 1e6 if med[k] else None for k in med}, "rounds_ms": res}
+
+
+def search_line(pkg, ctx, w, h, n_frames, gop, kind, quality, radius):
+    """the keys --search adds to a quality's line: the clip under both motion searches"""
+    st = pkg.SyntheticStream(w, h, kind=kind)
+    out = {"search_radius": radius}
+    for key, mode in (("four", "fourstep"), ("full", "full")):
+        buf = io.BytesIO()
+        enc = pkg.Encoder(buf, w, h, 30, quality, ctx, frame_report=True)
+        sess = pkg.EncoderSession(ctx, w, h, quality, 1)
+        enc.set_motion_search(mode, radius if mode == "full" else 0)
+        sess.set_motion_search(mode, radius if mode == "full" else 0)
+        coded = skipped = 0
+        psnr = []
+        for t in range(n_frames):
+            f = st.frame(t)
+            (enc.encode_iframe if t % gop == 0 else enc.encode_pframe)(pkg.VideoFrame.from_packed(w, h, f))
+            psnr.append(enc.last_report.psnr_yuv)
+            if t % gop == 0:
+                sess.encode_iframe(f)
+            else:
+                _, has, _ = sess.encode_pframe(f)
+                coded, skipped = coded + int((has != 0).sum()), skipped + int((has == 0).sum())
+        enc.finish()
+        enc.close()
+        sess.close()
+        out.update({f"{key}_stream_bytes": len(buf.getvalue()), f"{key}_psnr_yuv": float(sum(psnr) / len(psnr)), f"{key}_coded": coded, f"{key}_skipped": skipped})
+    return out
+
+
+def time_search(pkg, ctx, n_streams=96, w=1920, h=1080, quality=5, warmup=5, samples=30, rounds=3):
+    """pfv_enc_pframe_dev of frame 1 behind frame 0 as an i-frame: the default p-frame encode against PFV_SEARCH_FULL at R = 7 and R = 15 (two
+    launches each: k_pf_search_full + k_pf_transform).  A p-frame encode moves prev_frame: the i-frame that restores it is enqueued OUTSIDE the
+    event pair.  Medians of HIP-event times on the context's stream, the three alternating in every round"""
+    lib = ctx._lib
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    f0, f1 = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    enc = pkg.EncoderSession(ctx, w, h, quality, n_streams)
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(mode, radius):
+        enc.set_motion_search(mode, radius)
+        got, coded = [], 0
+        for k in range(warmup + samples):
+            enc.encode_iframe_dev(f0, coef)
+            ctx.record(e0)
+            enc.encode_pframe_dev(f1, mv, has, coef)
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        flags = np.zeros(n_streams * tb, np.uint8)
+        ctx.download(flags, has)
+        return statistics.median(got), int(flags.sum())
+    cases = {"fourstep": ("fourstep", 0), "full_r7": ("full", 7), "full_r15": ("full", 15)}
+    res, coded = {k: [] for k in cases}, {}
+    for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
+        for key, (mode, radius) in cases.items():
+            ms, coded[key] = median_ms(mode, radius)
+            res[key].append(ms)
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    enc.close()
+    for p in (f0, f1, coef, mv, has):
+        ctx.free(p)
+    med = {k: statistics.median(v) for k, v in res.items()}
+    # the products alone: (2R + 1)^2 candidates x 64 v_dot4 per macroblock, spread over its 8 lanes = (2R + 1)^2 x 8 wave-instructions per
+    # wavefront of 8 macroblocks (partial strips make the wavefronts a few more than macroblocks / 8)
+    waves = n_streams * int(lib.pfv_total_blocks(w, h)) / 8.0
+    floor = {k: waves * (2 * r + 1) ** 2 * 8 * 4.2 / 1024 / 2.4e9 * 1e3 for k, (_, r) in cases.items() if r}
+    over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
+    return {"shape": f"{n_streams} x {w}x{h}", "streams": n_streams, "quality": quality, "samples_per_round": samples, "rounds": rounds,
+            **{f"{k}_ms": v for k, v in med.items()}, **{f"{k}_over_fourstep": over(med[k], med["fourstep"]) for k in floor},
+            **{f"{k}_dot4_floor_ms": v for k, v in floor.items()}, **{f"{k}_over_floor": over(med[k], floor[k]) for k in floor},
+            "coded_macroblocks": coded, "macroblocks": n_streams * tb, "rounds_ms": res}
 
 
 def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
@@ -1208,6 +1298,8 @@ def main():
     ap.add_argument("--time-scale", action="store_true")
     ap.add_argument("--denoise", default=None, metavar="SS,ST")
     ap.add_argument("--time-denoise", action="store_true")
+    ap.add_argument("--search", default=None, metavar="full[,R]")
+    ap.add_argument("--time-search", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -1219,7 +1311,15 @@ def main():
             if a.denoise:
                 ss, st = (int(x) for x in a.denoise.split(","))
                 line.update(denoise_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, ss, st, dump=a.dump))
+            if a.search:
+                parts = a.search.split(",")
+                assert parts[0] == "full" and len(parts) <= 2, "--search full[,R]"
+                line.update(search_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, int(parts[1]) if len(parts) == 2 else 15))
             print(json.dumps(line), flush=True)
+        if a.time_search:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the row only
+            kw = dict(n_streams=2, w=a.width, h=a.height, warmup=1, samples=2, rounds=1) if emu else {}
+            print(json.dumps({"time_search": time_search(pkg, ctx, **kw)}), flush=True)
         if a.time_ssim:
             print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
         if a.time_deblock:
