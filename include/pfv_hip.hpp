@@ -255,7 +255,7 @@ inline std::vector<uint8_t> frames_denoise(Context &ctx, size_t width, size_t he
 }
 
 // motion search of an encoder session and of the stream encoders over it (pfv_*_set_motion_search): FourStep is the reference's search
-enum class MotionSearch { FourStep = PFV_SEARCH_FOURSTEP, Full = PFV_SEARCH_FULL };
+enum class MotionSearch { FourStep = PFV_SEARCH_FOURSTEP, Full = PFV_SEARCH_FULL, Hier = PFV_SEARCH_HIER };
 
 // The hot-path half of enc::Encoder for n streams (pfv_enc_session): packed frames of all streams in, the macroblock arrays out.
 class EncoderSession {
@@ -271,13 +271,20 @@ class EncoderSession {
     EncoderSession &operator=(const EncoderSession &) = delete;
     pfv_enc_session *handle() const { return h_; }
     size_t total_blocks() const { return blocks_; }
-    // the search of the p-frame launches that follow; radius 1 .. 15 for Full, ignored for FourStep
+    // the search of the p-frame launches that follow; radius 1 .. 15 for Full, even 2 .. 62 for Hier, ignored for FourStep
     void set_motion_search(MotionSearch mode, int radius = 0) { ctx_.check(pfv_enc_session_set_motion_search(h_, (int)mode, radius)); }
     std::pair<MotionSearch, int> motion_search() const
     {
         int m = 0, r = 0;
         ctx_.check(pfv_enc_session_get_motion_search(h_, &m, &r));
         return {(MotionSearch)m, r};
+    }
+    // the coarse level's vectors of the last p-frame launch, which was a Hier one: [stream][macroblock][2], half-resolution pixels
+    std::vector<int8_t> coarse_vectors() const
+    {
+        std::vector<int8_t> out(blocks_ * (size_t)n_ * 2);
+        ctx_.check(pfv_enc_session_coarse_vectors(h_, out.data(), out.size()));
+        return out;
     }
     struct PFrame {
         std::vector<int8_t> mv;          // [stream][macroblock][2]
@@ -413,7 +420,7 @@ class Encoder {
     void set_frame_ssim(bool on) { ctx_.check(pfv_encoder_set_frame_ssim(h_, on ? 1 : 0)); }
     // quality ladder: the rung of the frames that follow / of the last frame written (before the first frame: the current rung)
     void set_rung(int rung) { ctx_.check(pfv_encoder_set_rung(h_, rung)); }
-    // the search of the p-frames that follow; Full excludes the p-frame probe, the p-frame floors and encode_frame
+    // the search of the p-frames that follow; Full and Hier exclude the p-frame probe, the p-frame floors and encode_frame
     void set_motion_search(MotionSearch mode, int radius = 0) { ctx_.check(pfv_encoder_set_motion_search(h_, (int)mode, radius)); }
     int rung() const { return pfv_encoder_rung(h_); }
     int n_rungs() const { return pfv_encoder_rungs(h_); }

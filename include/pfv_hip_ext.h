@@ -683,11 +683,45 @@ PFV_API int pfv_encoder_set_denoise(pfv_encoder *e, int on, const uint8_t spatia
  * probes, budget and floors are unaffected.  pfv_gop_encoder: a batch that is made again (arena outgrown) takes the encoder's mode;
  * a change while a batch is in flight is refused with PFV_ERR_STATE (pfv_gop_encoder_flush first).  pfv_batch_encoder and the plane operator
  * pfv_encode_plane_delta have no switch. */
-enum { PFV_SEARCH_FOURSTEP = 0, PFV_SEARCH_FULL = 1 };
+enum { PFV_SEARCH_FOURSTEP = 0, PFV_SEARCH_FULL = 1, PFV_SEARCH_HIER = 2 };
 PFV_API int pfv_enc_session_set_motion_search(pfv_enc_session *s, int mode, int radius);
 PFV_API int pfv_enc_session_get_motion_search(pfv_enc_session *s, int *mode, int *radius);   /* either pointer may be NULL */
 PFV_API int pfv_encoder_set_motion_search(pfv_encoder *e, int mode, int radius);
 /* pfv_gop_encoder_set_motion_search: with the GOP encoder below */
+
+/* ------------------------------------------------------------------ wide-range hierarchical motion search  [B]
+ * The format writes a vector component as a 7-bit two's-complement field (src/enc.rs:421-446, src/dec.rs:367-368): -64 .. 63 pixels.  The
+ * four-step search and PFV_SEARCH_FULL stop at +-15.  PFV_SEARCH_HIER = 2 is a third MODE of the three setters above: a coarse search on
+ * planes of half the size, then a fine search round twice the coarse vector.  Like FULL its streams are ordinary .pfv streams but not the
+ * reference encoder's bytes, and with the mode off no launch and no byte changes.
+ * radius: EVEN, 2 .. 62 -- the coarse level's reach in full-resolution pixels, Rc = radius / 2.  Anything else: PFV_ERR_BAD_ARG, the mode
+ * stays as it was.  _get_motion_search reads back (2, radius).
+ *
+ * The rule (normative), per plane (Y, U, V are searched independently), the plane padded to pw x ph.  S is the padded source: the plane
+ * inside w x h, the plane's clear value outside.  P is the session's previous reconstruction.
+ *   1. half planes   hS[y][x] = (S[2y][2x] + S[2y][2x+1] + S[2y+1][2x] + S[2y+1][2x+1] + 2) >> 2, of size pw/2 x ph/2; hP from P likewise.
+ *   2. coarse level  for the macroblock at (bx, by): the 8 x 8 block of hS at (bx/2, by/2); candidates all (cx, cy) with |cx|, |cy| <= Rc,
+ *                    0 <= bx/2 + cx <= pw/2 - 8, 0 <= by/2 + cy <= ph/2 - 8; Ec the exact integer SSD over the 64 pixels (< 2^22); chosen
+ *                    c = the lexicographic minimum of (Ec, |cx| + |cy|, cy, cx).
+ *   3. fine level    at full resolution: candidates (0, 0) and every (2cx + rx, 2cy + ry) with |rx|, |ry| <= 2; each must satisfy
+ *                    |dx|, |dy| <= 63 and lie inside the plane (0 <= bx + dx <= pw - 16, 0 <= by + dy <= ph - 16); E the exact 16 x 16 SSD as
+ *                    in FULL; chosen = the lexicographic minimum of (E, |dx| + |dy|, dy, dx).  So E <= E(0, 0) always.
+ *   4. behind the choice the existing operator, exactly as in FULL: has_coef = !((float)E <= px_err^2 * 256) at the launch's rung; a
+ *      skipped macroblock has zero coefficients and the patch as its reconstruction; a coded one goes to k_pf_transform.
+ * Launches (csrc/pfv_hiersearch_kernels.hip): k_halve on the source and on the reference, k_pf_search_coarse, k_pf_refine, k_pf_transform.
+ * The outputs have the four-step launch's layout: rungs, windows, frame strides, by-reference slots, the ingest / scale / denoise stages,
+ * the device entropy stage and the distortion / SSIM reports work unchanged.  Cost: profiles/hier_search.md.
+ * The half planes and the coarse vectors are session scratch, allocated by the set_motion_search(HIER) call for all slots (PFV_ERR_NOMEM:
+ * the mode stays as it was), never inside an encode call, and freed by pfv_enc_session_destroy.
+ * Everything FULL refuses HIER refuses the same way (PFV_ERR_STATE): the p-frame probes, pfv_encoder_set_pframe_probe and the p-frame
+ * quality / SSIM floors in both directions, pfv_encoder_encode_frame, a change on a pfv_gop_encoder with a batch in flight.
+ * [C] pfv_enc_session_coarse_vectors: the coarse vectors (step 2) of the last p-frame launch over the current window, int8
+ * [slot][macroblock][2], n_bytes = 2 * macroblocks * slots of the window; waits for the stream.  PFV_ERR_STATE when the last p-frame launch
+ * was not a HIER one. */
+PFV_API int pfv_enc_session_coarse_vectors(pfv_enc_session *s, int8_t *out, size_t n_bytes);
+/* [C] pfv_enc_pframe_dev of a session in HIER mode (PFV_ERR_STATE otherwise) with an event in front of every kernel and behind the last; waits.
+ * ms_out[5]: k_halve of the source, k_halve of the reference, k_pf_search_coarse, k_pf_refine, k_pf_transform.  tools/rd_curve.py --time-search. */
+PFV_API int pfv_enc_pframe_hier_timed_dev(pfv_enc_session *s, const uint8_t *frames_dev, int8_t *mv_dev, uint8_t *has_coef_dev, int16_t *coef_dev, float ms_out[5]);
 
 /* ------------------------------------------------------------------ quality ladder, p-frame byte budget  [B]
  * The format lets a header carry any number of q-tables and every packet name its three tables by index (src/dec.rs:89-111, :244-246); the

@@ -10,7 +10,7 @@ The directory name contains a hyphen, so import it through
 ``__graft_entry__.load_package()`` (alias ``pretty_fast_video_amd``).
 """
 from . import _lib
-from ._lib import PfvError, PFV_SEARCH_FOURSTEP, PFV_SEARCH_FULL
+from ._lib import PfvError, PFV_SEARCH_FOURSTEP, PFV_SEARCH_FULL, PFV_SEARCH_HIER
 from .context import Context, Graph
 from .plane import VideoPlane, EncodedIPlane, EncodedPPlane
 from .frame import VideoFrame
@@ -23,4 +23,4 @@ from .denoise import Denoiser, frames_denoise
 from .quality import FrameReport, FrameSsim, deblock_strength, frames_deblock, frames_from_rgb, frames_sse, frames_to_rgb, frames_ssim, psnr, ssim, ssim_windows
 
 __all__ = ["Context", "Graph", "VideoPlane", "VideoFrame", "EncodedIPlane", "EncodedPPlane", "EncoderSession",
-           "DecoderSession", "Encoder", "BatchEncoder", "GopEncoder", "Decoder", "BatchDecoder", "GopDecoder", "DecodeError", "qtables_from_quality", "PfvError", "SyntheticStream", "FrameReport", "frames_sse", "psnr", "FrameSsim", "frames_ssim", "ssim", "ssim_windows", "frames_deblock", "deblock_strength", "frames_to_rgb", "frames_from_rgb", "Scaler", "frames_scale", "scale_table", "scale_taps", "Denoiser", "frames_denoise", "PFV_SEARCH_FOURSTEP", "PFV_SEARCH_FULL", "_lib"]
+           "DecoderSession", "Encoder", "BatchEncoder", "GopEncoder", "Decoder", "BatchDecoder", "GopDecoder", "DecodeError", "qtables_from_quality", "PfvError", "SyntheticStream", "FrameReport", "frames_sse", "psnr", "FrameSsim", "frames_ssim", "ssim", "ssim_windows", "frames_deblock", "deblock_strength", "frames_to_rgb", "frames_from_rgb", "Scaler", "frames_scale", "scale_table", "scale_taps", "Denoiser", "frames_denoise", "PFV_SEARCH_FOURSTEP", "PFV_SEARCH_FULL", "PFV_SEARCH_HIER", "_lib"]

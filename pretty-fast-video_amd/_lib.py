@@ -40,14 +40,14 @@ PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_d
 PFV_PIX_RGB8, PFV_PIX_RGBA8, PFV_PIX_BGRA8 = 0, 1, 2             # pixel formats of pfv_frames_to_rgb* and the decoders' RGB outputs
 PFV_CHROMA_POINT, PFV_CHROMA_BOX = 0, 1                          # chroma modes of pfv_frames_from_rgb* and the encoders' RGB inputs
 PFV_SCALE_BILINEAR, PFV_SCALE_BICUBIC, PFV_SCALE_LANCZOS3 = 0, 1, 2   # filter kinds of pfv_scaler_create / pfv_frames_scale
-PFV_SEARCH_FOURSTEP, PFV_SEARCH_FULL = 0, 1                           # motion search of an encoder session (pfv_*_set_motion_search)
+PFV_SEARCH_FOURSTEP, PFV_SEARCH_FULL, PFV_SEARCH_HIER = 0, 1, 2       # motion search of an encoder session (pfv_*_set_motion_search)
 
 
-SEARCH_MODES = {"fourstep": PFV_SEARCH_FOURSTEP, "full": PFV_SEARCH_FULL}
+SEARCH_MODES = {"fourstep": PFV_SEARCH_FOURSTEP, "full": PFV_SEARCH_FULL, "hier": PFV_SEARCH_HIER}
 
 
 def search_mode(mode) -> int:
-    """"fourstep" / "full" or a PFV_SEARCH_* value"""
+    """"fourstep" / "full" / "hier" or a PFV_SEARCH_* value"""
     return SEARCH_MODES[mode] if isinstance(mode, str) else int(mode)
 
 
@@ -216,6 +216,8 @@ SIGNATURES = [
     ("pfv_enc_session_set_motion_search", c_int, [_P, c_int, c_int]),
     ("pfv_enc_session_get_motion_search", c_int, [_P, _P, _P]),
     ("pfv_encoder_set_motion_search", c_int, [_P, c_int, c_int]),
+    ("pfv_enc_session_coarse_vectors", c_int, [_P, _P, c_size_t]),
+    ("pfv_enc_pframe_hier_timed_dev", c_int, [_P, _P, _P, _P, _P, _P]),
     ("pfv_enc_session_set_rung", c_int, [_P, c_int]),
     ("pfv_enc_session_rung", c_int, [_P]),
     ("pfv_enc_session_rungs", c_int, [_P]),

@@ -21,6 +21,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #include "pfv_deblock_kernels.hip"
 #include "pfv_denoise_kernels.hip"
 #include "pfv_fullsearch_kernels.hip"
+#include "pfv_hiersearch_kernels.hip"
 #include "pfv_entropy_kernels.hip"
 #include "pfv_probe_kernels.hip"
 #include "pfv_rdprobe_kernels.hip"

@@ -169,6 +169,42 @@ static void launch_enc_pframe_full(pfv_ctx *ctx, bool flt, int radius, const Fra
     if (flt) hipLaunchKernelGGL(k_pf_transform<true>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
     else hipLaunchKernelGGL(k_pf_transform<false>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
 }
+// PFV_SEARCH_HIER (pfv_hiersearch_kernels.hip): the half planes of a slot, Y | U | V, every row pitch a multiple of 16 bytes
+static HalfGeom half_geom(const FrameGeom &g)
+{
+    HalfGeom hg{};
+    long off = 0;
+    for (int i = 0; i < g.n_planes; i++) {
+        hg.pitch[i] = (g.p[i].pw / 2 + 15) & ~15;
+        hg.off[i] = off;
+        off += (long)hg.pitch[i] * (g.p[i].ph / 2);
+    }
+    hg.frame_bytes = off;
+    return hg;
+}
+// The half planes of the source and of the reference, the coarse search on them, the fine search round twice the coarse vector, then the
+// split form's transform kernel on the coded macroblocks.  hsrc, href, cmv: session scratch of the launch's slots.
+static void launch_enc_pframe_hier(pfv_ctx *ctx, bool flt, int radius, const FrameGeom &g, const uint8_t *src, const uint8_t *ref, uint8_t *hsrc, uint8_t *href,
+                                   int8_t *cmv, int8_t *mv, uint8_t *has, int16_t *coef, uint8_t *recon, const QTab *qt, float min_err,
+                                   const hipEvent_t *marks = nullptr /* pfv_enc_pframe_hier_timed_dev: 6 events, one in front of every kernel and one behind */)
+{
+    const HalfGeom hg = half_geom(g);
+    const unsigned hb = (unsigned)(((hg.frame_bytes / 4) * g.n_streams + kThreads - 1) / kThreads);
+    auto mark = [&](int k) { if (marks) (void)hipEventRecord(marks[k], ctx->stream); };
+    mark(0);
+    hipLaunchKernelGGL(k_halve<false>, dim3(hb), dim3(kThreads), 0, ctx->stream, g, hg, src, hsrc);
+    mark(1);
+    hipLaunchKernelGGL(k_halve<true>, dim3(hb), dim3(kThreads), 0, ctx->stream, g, hg, ref, href);
+    mark(2);
+    hipLaunchKernelGGL(k_pf_search_coarse, dim3(penc_blocks(ctx, g)), dim3(kThreads), 0, ctx->stream, g, hg, (const uint8_t *)hsrc, (const uint8_t *)href, cmv, radius / 2);
+    mark(3);
+    hipLaunchKernelGGL(k_pf_refine, dim3(strip_blocks(g)), dim3(kThreads), 0, ctx->stream, g, src, ref, (const int8_t *)cmv, mv, has, coef, recon, min_err);
+    mark(4);
+    const unsigned tf = (unsigned)((long)g.n_streams * tf_groups_per_frame(g));
+    if (flt) hipLaunchKernelGGL(k_pf_transform<true>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
+    else hipLaunchKernelGGL(k_pf_transform<false>, dim3(tf), dim3(64), 0, ctx->stream, g, src, ref, (const int8_t *)mv, (const uint8_t *)has, coef, recon, qt, kQuantMagic);
+    mark(5);
+}
 // where a decode launch finds its coefficients: the dense [slot][macroblock][256] array, or coefficient lists (pfv_device.h: CoefLists)
 struct DecCoefs {
     const int16_t *dense = nullptr;

@@ -93,7 +93,12 @@ struct pfv_enc_session {
     int tile_compaction = 1;                 // PFV_OPT_TILE_COMPACTION at creation
     int lane_mapping = PFV_LANES_AUTO;       // PFV_OPT_LANE_MAPPING at creation
     int search_mode = PFV_SEARCH_FOURSTEP;   // pfv_enc_session_set_motion_search: applies to the p-frame launches that follow
-    int search_radius = 0;                   // PFV_SEARCH_FULL: 1..15
+    int search_radius = 0;                   // PFV_SEARCH_FULL: 1..15; PFV_SEARCH_HIER: even, 2..62
+    // PFV_SEARCH_HIER scratch, allocated by pfv_enc_session_set_motion_search for all slots: the half planes of the source and of the
+    // reference ([n_streams] x HalfGeom::frame_bytes each) and the coarse vectors [n_streams][macroblock][2]
+    uint8_t *hier_src = nullptr, *hier_ref = nullptr;
+    int8_t *hier_cmv = nullptr;
+    bool hier_launched = false;              // the last p-frame launch was a HIER one: hier_cmv holds its window's coarse vectors
     uint8_t *prev[2] = {nullptr, nullptr};   // ping-pong prev_frame, padded, n_streams wide
     int cur = 0;                             // prev[cur] is the current prev_frame
     int win_first = 0, win_count = 0;        // slot window of the *_dev / pack calls (pfv_enc_session_set_window)
@@ -266,10 +271,27 @@ PFV_API int pfv_enc_session_rung(pfv_enc_session *s) { return s ? s->rung : PFV_
 PFV_API int pfv_enc_session_set_motion_search(pfv_enc_session *s, int mode, int radius)
 {
     if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
-    if (mode != PFV_SEARCH_FOURSTEP && mode != PFV_SEARCH_FULL) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: unknown mode");
+    if (mode != PFV_SEARCH_FOURSTEP && mode != PFV_SEARCH_FULL && mode != PFV_SEARCH_HIER) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: unknown mode");
     if (mode == PFV_SEARCH_FULL && (radius < 1 || radius > 15)) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: the radius of the full search is 1..15");
+    if (mode == PFV_SEARCH_HIER && (radius < 2 || radius > 62 || (radius & 1))) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_set_motion_search: the radius of the hierarchical search is even, 2..62");
+    if (mode == PFV_SEARCH_HIER && !s->hier_cmv) {   // here and never inside an encode call: a launch recorded in a graph only replays kernels
+        pfv_ctx *ctx = s->ctx;
+        if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, PFV_ERR_HIP, "pfv_enc_session_set_motion_search: hipSetDevice");
+        const size_t half = (size_t)half_geom(s->geom).frame_bytes * s->n_streams;
+        uint8_t *hs = nullptr, *hr = nullptr;
+        int8_t *cv = nullptr;
+        if (hipMalloc((void **)&hs, half) != hipSuccess || hipMalloc((void **)&hr, half) != hipSuccess ||
+            hipMalloc((void **)&cv, (size_t)s->geom.mbs_per_frame * s->n_streams * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            if (hs) (void)hipFree(hs);
+            if (hr) (void)hipFree(hr);
+            if (cv) (void)hipFree(cv);
+            return fail(ctx, PFV_ERR_NOMEM, "pfv_enc_session_set_motion_search: no device memory for the half planes of the hierarchical search");
+        }
+        s->hier_src = hs; s->hier_ref = hr; s->hier_cmv = cv;
+    }
     s->search_mode = mode;
-    s->search_radius = mode == PFV_SEARCH_FULL ? radius : 0;
+    s->search_radius = mode == PFV_SEARCH_FOURSTEP ? 0 : radius;
     return PFV_OK;
 }
 PFV_API int pfv_enc_session_get_motion_search(pfv_enc_session *s, int *mode, int *radius)
@@ -279,10 +301,24 @@ PFV_API int pfv_enc_session_get_motion_search(pfv_enc_session *s, int *mode, int
     if (radius) *radius = s->search_radius;
     return PFV_OK;
 }
-// the p-frame probes restate the four-step front end (probe_tile_front): under the full search they would size another encoder's frames
+// the p-frame probes restate the four-step front end (probe_tile_front): under another search they would size another encoder's frames
+static bool enc_fourstep(const pfv_enc_session *s) { return s->search_mode == PFV_SEARCH_FOURSTEP; }
 static int enc_pframe_probe_refused(pfv_enc_session *s, const char *who)
 {
-    if (s && s->search_mode == PFV_SEARCH_FULL) return fail(s->ctx, PFV_ERR_STATE, std::string(who) + ": the p-frame probes follow the four-step search; the session is in PFV_SEARCH_FULL");
+    if (s && !enc_fourstep(s)) return fail(s->ctx, PFV_ERR_STATE, std::string(who) + ": the p-frame probes follow the four-step search; the session is in PFV_SEARCH_FULL or PFV_SEARCH_HIER");
+    return PFV_OK;
+}
+// [C] the coarse vectors of the last p-frame launch, which was a PFV_SEARCH_HIER one, over the current window: int8 [slot][macroblock][2]
+PFV_API int pfv_enc_session_coarse_vectors(pfv_enc_session *s, int8_t *out, size_t n_bytes)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    pfv_ctx *ctx = s->ctx;
+    if (!s->hier_launched) return fail(ctx, PFV_ERR_STATE, "pfv_enc_session_coarse_vectors: the last p-frame launch was not a PFV_SEARCH_HIER one");
+    const size_t per = (size_t)s->geom.mbs_per_frame * 2;
+    if (!out || n_bytes != per * (size_t)s->win_count) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_session_coarse_vectors: out must hold 2 bytes per macroblock of the window's slots");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(out, s->hier_cmv + per * (size_t)s->win_first, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFV_OK;
 }
 PFV_API int pfv_enc_session_rungs(pfv_enc_session *s) { return s ? s->n_rungs : PFV_ERR_BAD_ARG; }
@@ -292,7 +328,7 @@ PFV_API void pfv_enc_session_destroy(pfv_enc_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->scale_frames, s->denoise_frames, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
+    void *bufs[] = {s->qtab_dev, s->prev[0], s->prev[1], s->st_frames, s->st_coef, s->st_mv, s->st_has, s->ingest_frames, s->scale_frames, s->denoise_frames, s->hier_src, s->hier_ref, s->hier_cmv, s->q_map, s->q_sse, s->ssim_map, s->ssim_sums, s->probe_acc, s->probe_sizes, s->rd_acc, s->rd_out, s->pprobe_acc, s->pprobe_out, s->prd_out, s->ssim_probe_map, s->ssim_probe_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (void *b : s->ent_allocs)
@@ -326,7 +362,7 @@ static FrameGeom enc_win_geom(const pfv_enc_session *s, int count, const uint8_t
 // slots_dev (pfv_gop_encoder with frames taken by reference): a device table of one frame pointer per slot, every pointer 16-byte aligned;
 // slot k of the session reads the packed frame at slots_dev[k] instead of frames_dev + k * stride
 static int enc_launch(pfv_enc_session *s, bool pframe, int first, int count, const uint8_t *frames_dev, int8_t *mv_dev, uint8_t *has_dev,
-                      int16_t *coef_dev, const uint8_t *const *slots_dev = nullptr)
+                      int16_t *coef_dev, const uint8_t *const *slots_dev = nullptr, const hipEvent_t *hier_marks = nullptr)
 {
     pfv_ctx *ctx = s->ctx;
     const size_t stride = s->in_stride ? s->in_stride : (size_t)s->geom.src_frame_bytes;
@@ -337,11 +373,19 @@ static int enc_launch(pfv_enc_session *s, bool pframe, int first, int count, con
     const int nxt = s->cur ^ 1;
     const QTab *rung_tabs = s->qtab_dev + 4 * s->rung;           // the rung of this launch: its four tables, its px_err
     if (pframe) {
+        s->hier_launched = false;
         const float min_err = s->px_err[s->rung] * s->px_err[s->rung] * 256.0f;   // src/common.rs:209
         if (s->search_mode == PFV_SEARCH_FULL) {
             launch_enc_pframe_full(ctx, s->flt, s->search_radius, g, src, s->prev[s->cur] + pad0, mv_dev + mb0 * 2, has_dev + mb0, coef_dev + mb0 * 256,
                                    s->prev[nxt] + pad0, rung_tabs + 2, min_err);
             return launch_check(ctx, "k_pf_search_full");
+        }
+        if (s->search_mode == PFV_SEARCH_HIER) {
+            const size_t half0 = (size_t)first * (size_t)half_geom(s->geom).frame_bytes;
+            launch_enc_pframe_hier(ctx, s->flt, s->search_radius, g, src, s->prev[s->cur] + pad0, s->hier_src + half0, s->hier_ref + half0, s->hier_cmv + mb0 * 2,
+                                   mv_dev + mb0 * 2, has_dev + mb0, coef_dev + mb0 * 256, s->prev[nxt] + pad0, rung_tabs + 2, min_err, hier_marks);
+            s->hier_launched = true;
+            return launch_check(ctx, "k_pf_search_coarse");
         }
         launch_enc_pframe(ctx, s->flt, use_small_grid(s->lane_mapping, g), s->tile_compaction, g, src, s->prev[s->cur] + pad0, mv_dev + mb0 * 2,
                           has_dev + mb0, coef_dev + mb0 * 256, s->prev[nxt] + pad0, rung_tabs + 2, min_err);
@@ -387,6 +431,29 @@ PFV_API int pfv_enc_pframe_dev(pfv_enc_session *s, const uint8_t *frames_dev, in
     if (!frames_dev || !mv_dev || !has_coef_dev || !coef_dev) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_pframe_dev: null buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = enc_launch(s, true, s->win_first, s->win_count, frames_dev, mv_dev, has_coef_dev, coef_dev);
+    if (rc) return rc;
+    s->cur ^= 1;
+    return PFV_OK;
+}
+
+// [C] pfv_enc_pframe_dev in PFV_SEARCH_HIER mode with an event in front of every kernel and behind the last: ms_out[5] = k_halve of the
+// source, k_halve of the reference, k_pf_search_coarse, k_pf_refine, k_pf_transform.  Same outputs, same step of the session; waits.
+PFV_API int pfv_enc_pframe_hier_timed_dev(pfv_enc_session *s, const uint8_t *frames_dev, int8_t *mv_dev, uint8_t *has_coef_dev, int16_t *coef_dev, float ms_out[5])
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    pfv_ctx *ctx = s->ctx;
+    if (!frames_dev || !mv_dev || !has_coef_dev || !coef_dev || !ms_out) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_enc_pframe_hier_timed_dev: null buffer");
+    if (s->search_mode != PFV_SEARCH_HIER) return fail(ctx, PFV_ERR_STATE, "pfv_enc_pframe_hier_timed_dev: the session is not in PFV_SEARCH_HIER");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipEvent_t ev[6] = {};
+    auto drop = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
+    for (hipEvent_t &e : ev)
+        if (hipEventCreateWithFlags(&e, hipEventDefault) != hipSuccess) { drop(); return fail(ctx, PFV_ERR_HIP, "pfv_enc_pframe_hier_timed_dev: hipEventCreate"); }
+    int rc = enc_launch(s, true, s->win_first, s->win_count, frames_dev, mv_dev, has_coef_dev, coef_dev, nullptr, ev);
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, PFV_ERR_HIP, "pfv_enc_pframe_hier_timed_dev: hipStreamSynchronize");
+    for (int k = 0; k < 5 && !rc; k++)
+        if (hipEventElapsedTime(&ms_out[k], ev[k], ev[k + 1]) != hipSuccess) rc = fail(ctx, PFV_ERR_HIP, "pfv_enc_pframe_hier_timed_dev: hipEventElapsedTime");
+    drop();
     if (rc) return rc;
     s->cur ^= 1;
     return PFV_OK;

@@ -605,7 +605,7 @@ PFV_API int pfv_encoder_set_pframe_quality_floor(pfv_encoder *e, double min_psnr
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!(min_psnr_yuv >= 0.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_quality_floor: the floor must be >= 0 dB (+INFINITY is legal, NaN is not)");
-    if (min_psnr_yuv > 0.0 && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_quality_floor: the p-frame probes do not follow PFV_SEARCH_FULL");
+    if (min_psnr_yuv > 0.0 && !enc_fourstep(e->hot)) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_quality_floor: the p-frame probes follow the four-step search only");
     e->floor_p = min_psnr_yuv;
     return PFV_OK;
 }
@@ -622,7 +622,7 @@ PFV_API int pfv_encoder_set_pframe_ssim_floor(pfv_encoder *e, double min_ssim)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
     if (!(min_ssim >= 0.0 && min_ssim <= 1.0)) return fail(e->ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_pframe_ssim_floor: the floor must lie in [0, 1] (NaN is not legal)");
-    if (min_ssim > 0.0 && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_ssim_floor: the p-frame probes do not follow PFV_SEARCH_FULL");
+    if (min_ssim > 0.0 && !enc_fourstep(e->hot)) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_ssim_floor: the p-frame probes follow the four-step search only");
     e->sfloor_p = min_ssim;
     return PFV_OK;
 }
@@ -1125,7 +1125,7 @@ PFV_API int pfv_encoder_probe_pframe_ssim(pfv_encoder *e, const uint8_t *y, cons
 PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (on && e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_probe: the p-frame probes do not follow PFV_SEARCH_FULL");
+    if (on && !enc_fourstep(e->hot)) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_pframe_probe: the p-frame probes follow the four-step search only");
     e->pprobe_on = on != 0;
     return PFV_OK;
 }
@@ -1133,8 +1133,9 @@ PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on)
 PFV_API int pfv_encoder_set_motion_search(pfv_encoder *e, int mode, int radius)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (mode == PFV_SEARCH_FULL && radius >= 1 && radius <= 15 && (e->pprobe_on || e->floor_p > 0.0 || e->sfloor_p > 0.0))
-        return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_motion_search: the p-frame probe and the p-frame floors do not follow PFV_SEARCH_FULL: switch them off first");
+    const bool valid = (mode == PFV_SEARCH_FULL && radius >= 1 && radius <= 15) || (mode == PFV_SEARCH_HIER && radius >= 2 && radius <= 62 && !(radius & 1));
+    if (valid && (e->pprobe_on || e->floor_p > 0.0 || e->sfloor_p > 0.0))
+        return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_set_motion_search: the p-frame probe and the p-frame floors follow the four-step search only: switch them off first");
     return pfv_enc_session_set_motion_search(e->hot, mode, radius);
 }
 PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval)
@@ -1232,7 +1233,7 @@ static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint6
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (e->hot->search_mode == PFV_SEARCH_FULL) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_encode_frame: the frame type comes from the p-frame probes, which do not follow PFV_SEARCH_FULL");
+    if (!enc_fourstep(e->hot)) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_encode_frame: the frame type comes from the p-frame probes, which follow the four-step search only");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
     e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state

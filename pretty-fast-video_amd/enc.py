@@ -87,8 +87,8 @@ class Encoder:
         self.ctx.check(self.ctx._lib.pfv_encoder_set_denoise(self.handle, 1 if on else 0, ptr(s), ptr(t)))
 
     def set_motion_search(self, mode="fourstep", radius: int = 0):
-        """the motion search of the p-frames that follow: "fourstep" or "full" with a radius of 1..15 (pfv_encoder_set_motion_search);
-        full mode excludes the p-frame probe, the p-frame floors and encode_frame"""
+        """the motion search of the p-frames that follow: "fourstep", "full" with a radius of 1..15 or "hier" with an even radius of 2..62
+        (pfv_encoder_set_motion_search); full and hier mode exclude the p-frame probe, the p-frame floors and encode_frame"""
         from ._lib import search_mode
         self.ctx.check(self.ctx._lib.pfv_encoder_set_motion_search(self.handle, search_mode(mode), int(radius)))
 
@@ -443,8 +443,8 @@ class GopEncoder(Encoder):
         self._flush()
 
     def set_motion_search(self, mode="fourstep", radius: int = 0):
-        """the motion search of the batches submitted from now on: "fourstep" or "full" with a radius of 1..15; refused while a batch is
-        in flight (pfv_gop_encoder_set_motion_search)"""
+        """the motion search of the batches submitted from now on: "fourstep", "full" with a radius of 1..15 or "hier" with an even radius
+        of 2..62; refused while a batch is in flight (pfv_gop_encoder_set_motion_search)"""
         from ._lib import search_mode
         self.ctx.check(self.ctx._lib.pfv_gop_encoder_set_motion_search(self.handle, search_mode(mode), int(radius)))
 

@@ -75,17 +75,34 @@ class EncoderSession(_Geometry):
 
     # motion search ------------------------------------------------------
     def set_motion_search(self, mode="fourstep", radius: int = 0):
-        """how the p-frame launches that follow choose their vectors: "fourstep" (the reference's search, the default) or "full" with a
-        radius of 1..15, every vector of the square (pfv_enc_session_set_motion_search); the p-frame probes are refused in full mode"""
+        """how the p-frame launches that follow choose their vectors: "fourstep" (the reference's search, the default), "full" with a
+        radius of 1..15, every vector of the square, or "hier" with an even radius of 2..62, a coarse search at half size and a fine one
+        round it (pfv_enc_session_set_motion_search); the p-frame probes are refused in full and hier mode"""
         from ._lib import search_mode
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_motion_search(self.handle, search_mode(mode), int(radius)))
 
     @property
     def motion_search(self):
-        """(mode, radius): PFV_SEARCH_FOURSTEP / PFV_SEARCH_FULL, and the radius (0 for four-step)"""
+        """(mode, radius): PFV_SEARCH_FOURSTEP / PFV_SEARCH_FULL / PFV_SEARCH_HIER, and the radius (0 for four-step)"""
         m, r = ctypes.c_int(), ctypes.c_int()
         self.ctx.check(self.ctx._lib.pfv_enc_session_get_motion_search(self.handle, ctypes.byref(m), ctypes.byref(r)))
         return int(m.value), int(r.value)
+
+    def coarse_vectors(self) -> np.ndarray:
+        """the coarse level's vectors of the last p-frame launch, which was a "hier" one, over the current window: int8
+        [slots, macroblocks, 2] in half-resolution pixels (pfv_enc_session_coarse_vectors; waits for the stream)"""
+        out = np.zeros((getattr(self, "_win_count", self.n_streams), self.total_blocks, 2), np.int8)
+        self.ctx.check(self.ctx._lib.pfv_enc_session_coarse_vectors(self.handle, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+        return out
+
+    HIER_STAGES = ("halve_src", "halve_ref", "coarse", "refine", "transform")
+
+    def encode_pframe_hier_timed_dev(self, frames_dev: int, mv_dev: int, has_dev: int, coef_dev: int) -> dict:
+        """encode_pframe_dev in "hier" mode with an event round every kernel: milliseconds per stage (pfv_enc_pframe_hier_timed_dev; waits)"""
+        ms = (ctypes.c_float * 5)()
+        self.ctx.check(self.ctx._lib.pfv_enc_pframe_hier_timed_dev(self.handle, ctypes.c_void_p(frames_dev), ctypes.c_void_p(mv_dev), ctypes.c_void_p(has_dev),
+                                                                   ctypes.c_void_p(coef_dev), ms))
+        return dict(zip(self.HIER_STAGES, (float(x) for x in ms)))
 
     # i-frame size probe -------------------------------------------------
     def probe_iframe(self, frames) -> np.ndarray:
@@ -250,8 +267,9 @@ class EncoderSession(_Geometry):
         self.ctx.check(self.ctx._lib.pfv_enc_session_set_frame_stride(self.handle, int(stride_bytes)))
 
     def set_window(self, first: int = 0, count: int | None = None):
-        self.ctx.check(self.ctx._lib.pfv_enc_session_set_window(self.handle, int(first), int(self.n_streams - first if count is None else count)))
-
+        count = int(self.n_streams - first if count is None else count)
+        self.ctx.check(self.ctx._lib.pfv_enc_session_set_window(self.handle, int(first), count))
+        self._win_count = count
 
     # device entropy stage (RLE + Huffman + bit packing of enc.rs:237-470 on the device) ---------------
     def enable_entropy(self, payload_cap: int = 0, async_stream: bool = False):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise] [--search full[,R]] [--time-search]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise] [--search full[,R]|hier,R] [--pan DX,DY] [--time-search]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -35,6 +35,14 @@ the samples, alternating in three rounds.  With PFV_HIP_LIB set only one WIDTH x
 --search full[,R] (R = 1 .. 15, default 15) adds, per quality, the clip encoded with both motion searches (pfv_encoder_set_motion_search) side by
 side: four_ / full_ stream_bytes, psnr_yuv (mean over the frames, frame reports), and the coded and skipped p-frame macroblocks (an encoder
 session fed the same frames); search_radius = R.
+
+--search hier,R (R even, 2 .. 62) adds the same columns for three encoders: four_ (four-step), full_ (PFV_SEARCH_FULL at radius 15) and hier_
+(PFV_SEARCH_HIER at radius R).  --pan DX,DY replaces the clip of the --search columns by a textured canvas seen through a window that moves by
+(DX, DY) pixels per frame (search_pan = [DX, DY]): a pan beyond +-15 is what the two-level search is for.
+
+--time-search also times PFV_SEARCH_HIER at radius 30 and 62: the whole p-frame launch (hier_r30_ms, hier_r62_ms) and, from
+pfv_enc_pframe_hier_timed_dev, its five kernels (hier_r30_stages_ms / hier_r62_stages_ms: k_halve of the source, k_halve of the reference,
+k_pf_search_coarse, k_pf_refine, k_pf_transform), with the v_dot4 floor of the coarse level's products ((2 Rc + 1)^2 x 16 per macroblock).
 
 --time-search (on the GPU box) adds one more line: k_pf_search_full + k_pf_transform at R = 7 and R = 15 against the default p-frame encode of
 the same 96 x 1080p frames (frame 1 of the synthetic streams behind frame 0 as an i-frame) -- HIP events on the context's stream around every
@@ -413,20 +421,43 @@ def time_denoise(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30, r
             **{f"{k}_GBps": moved[k] / med[k] / 1e6 if med[k] else None for k in med}, "rounds_ms": res}
 
 
-def search_line(pkg, ctx, w, h, n_frames, gop, kind, quality, radius):
-    """the keys --search adds to a quality's line: the clip under both motion searches"""
-    st = pkg.SyntheticStream(w, h, kind=kind)
+def pan_clip(w, h, n_frames, dx, dy, seed=7):
+    """packed frames of a smoothed random canvas seen through a window that moves by (dx, dy) per frame; chroma is the luma at the even positions"""
+    rng = np.random.default_rng(seed)
+    mx, my = abs(dx) * (n_frames - 1), abs(dy) * (n_frames - 1)
+    c = rng.integers(0, 256, (h + my + 2, w + mx + 2)).astype(np.int32)
+    c = (c[:-2, :-2] + c[1:-1, :-2] + c[2:, :-2] + c[:-2, 1:-1] + 2 * c[1:-1, 1:-1] + c[2:, 1:-1] + c[:-2, 2:] + c[1:-1, 2:] + c[2:, 2:]) // 10
+    c = np.clip((c - 128) * 3 + 128, 0, 255).astype(np.uint8)
+    out = []
+    for t in range(n_frames):
+        ox, oy = (t * dx if dx >= 0 else mx + t * dx), (t * dy if dy >= 0 else my + t * dy)
+        y = c[oy:oy + h, ox:ox + w]
+        u = y[::2, ::2][:h // 2, :w // 2]
+        out.append(np.concatenate([y.reshape(-1), u.reshape(-1), (255 - u).reshape(-1)]))
+    return out
+
+
+def search_line(pkg, ctx, w, h, n_frames, gop, kind, quality, radius, mode="full", pan=None):
+    """the keys --search adds to a quality's line: the clip under the four-step search and under `mode` at `radius` ("hier": and under the
+    exhaustive search at radius 15)"""
+    if pan:
+        clip = pan_clip(w, h, n_frames, *pan)
+    else:
+        st = pkg.SyntheticStream(w, h, kind=kind)
+        clip = [st.frame(t) for t in range(n_frames)]
     out = {"search_radius": radius}
-    for key, mode in (("four", "fourstep"), ("full", "full")):
+    if pan:
+        out["search_pan"] = list(pan)
+    cases = (("four", "fourstep", 0), ("full", "full", radius)) if mode == "full" else (("four", "fourstep", 0), ("full", "full", 15), ("hier", "hier", radius))
+    for key, m, r in cases:
         buf = io.BytesIO()
         enc = pkg.Encoder(buf, w, h, 30, quality, ctx, frame_report=True)
         sess = pkg.EncoderSession(ctx, w, h, quality, 1)
-        enc.set_motion_search(mode, radius if mode == "full" else 0)
-        sess.set_motion_search(mode, radius if mode == "full" else 0)
+        enc.set_motion_search(m, r)
+        sess.set_motion_search(m, r)
         coded = skipped = 0
         psnr = []
-        for t in range(n_frames):
-            f = st.frame(t)
+        for t, f in enumerate(clip):
             (enc.encode_iframe if t % gop == 0 else enc.encode_pframe)(pkg.VideoFrame.from_packed(w, h, f))
             psnr.append(enc.last_report.psnr_yuv)
             if t % gop == 0:
@@ -470,14 +501,26 @@ def time_search(pkg, ctx, n_streams=96, w=1920, h=1080, quality=5, warmup=5, sam
         flags = np.zeros(n_streams * tb, np.uint8)
         ctx.download(flags, has)
         return statistics.median(got), int(flags.sum())
-    cases = {"fourstep": ("fourstep", 0), "full_r7": ("full", 7), "full_r15": ("full", 15)}
-    res, coded = {k: [] for k in cases}, {}
+    def stages_ms(radius):
+        enc.set_motion_search("hier", radius)
+        got = []
+        for k in range(warmup + samples):
+            enc.encode_iframe_dev(f0, coef)
+            st = enc.encode_pframe_hier_timed_dev(f1, mv, has, coef)
+            if k >= warmup:
+                got.append(st)
+        return {name: statistics.median(g_[name] for g_ in got) for name in enc.HIER_STAGES}
+    cases = {"fourstep": ("fourstep", 0), "full_r7": ("full", 7), "full_r15": ("full", 15), "hier_r30": ("hier", 30), "hier_r62": ("hier", 62)}
+    res, coded, stages = {k: [] for k in cases}, {}, {"hier_r30": [], "hier_r62": []}
     for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
         for key, (mode, radius) in cases.items():
             ms, coded[key] = median_ms(mode, radius)
             res[key].append(ms)
+            if mode == "hier":
+                stages[key].append(stages_ms(radius))
     ctx.sync()
     ctx.event_destroy(e0); ctx.event_destroy(e1)
+    enc_stages = enc.HIER_STAGES
     enc.close()
     for p in (f0, f1, coef, mv, has):
         ctx.free(p)
@@ -485,12 +528,17 @@ def time_search(pkg, ctx, n_streams=96, w=1920, h=1080, quality=5, warmup=5, sam
     # the products alone: (2R + 1)^2 candidates x 64 v_dot4 per macroblock, spread over its 8 lanes = (2R + 1)^2 x 8 wave-instructions per
     # wavefront of 8 macroblocks (partial strips make the wavefronts a few more than macroblocks / 8)
     waves = n_streams * int(lib.pfv_total_blocks(w, h)) / 8.0
-    floor = {k: waves * (2 * r + 1) ** 2 * 8 * 4.2 / 1024 / 2.4e9 * 1e3 for k, (_, r) in cases.items() if r}
+    floor = {k: waves * (2 * r + 1) ** 2 * 8 * 4.2 / 1024 / 2.4e9 * 1e3 for k, (m_, r) in cases.items() if m_ == "full"}
+    # the coarse level: (2 Rc + 1)^2 candidates x 16 v_dot4 per macroblock over its 8 lanes
+    cfloor = {k: waves * (r + 1) ** 2 * 2 * 4.2 / 1024 / 2.4e9 * 1e3 for k, (m_, r) in cases.items() if m_ == "hier"}
+    hier = {f"{k}_stages_ms": {n: statistics.median(x[n] for x in v) for n in enc_stages} for k, v in stages.items()}
+    hier.update({f"{k}_coarse_dot4_floor_ms": v for k, v in cfloor.items()})
+    hier.update({f"{k}_coarse_over_floor": (hier[f"{k}_stages_ms"]["coarse"] / v if hier[f"{k}_stages_ms"]["coarse"] else None) for k, v in cfloor.items()})
     over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
     return {"shape": f"{n_streams} x {w}x{h}", "streams": n_streams, "quality": quality, "samples_per_round": samples, "rounds": rounds,
             **{f"{k}_ms": v for k, v in med.items()}, **{f"{k}_over_fourstep": over(med[k], med["fourstep"]) for k in floor},
             **{f"{k}_dot4_floor_ms": v for k, v in floor.items()}, **{f"{k}_over_floor": over(med[k], floor[k]) for k in floor},
-            "coded_macroblocks": coded, "macroblocks": n_streams * tb, "rounds_ms": res}
+            **hier, "coded_macroblocks": coded, "macroblocks": n_streams * tb, "rounds_ms": res}
 
 
 def time_present(pkg, ctx, fmt, n_streams=96, w=1920, h=1080, warmup=5, samples=30, rounds=3):
@@ -1298,7 +1346,8 @@ def main():
     ap.add_argument("--time-scale", action="store_true")
     ap.add_argument("--denoise", default=None, metavar="SS,ST")
     ap.add_argument("--time-denoise", action="store_true")
-    ap.add_argument("--search", default=None, metavar="full[,R]")
+    ap.add_argument("--search", default=None, metavar="full[,R]|hier,R")
+    ap.add_argument("--pan", default=None, metavar="DX,DY")
     ap.add_argument("--time-search", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
@@ -1313,8 +1362,9 @@ def main():
                 line.update(denoise_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, ss, st, dump=a.dump))
             if a.search:
                 parts = a.search.split(",")
-                assert parts[0] == "full" and len(parts) <= 2, "--search full[,R]"
-                line.update(search_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, int(parts[1]) if len(parts) == 2 else 15))
+                assert (parts[0] == "full" and len(parts) <= 2) or (parts[0] == "hier" and len(parts) == 2), "--search full[,R] or hier,R"
+                pan = tuple(int(x) for x in a.pan.split(",")) if a.pan else None
+                line.update(search_line(pkg, ctx, a.width, a.height, a.frames, a.gop, a.kind, q, int(parts[1]) if len(parts) == 2 else 15, mode=parts[0], pan=pan))
             print(json.dumps(line), flush=True)
         if a.time_search:
             emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the row only
