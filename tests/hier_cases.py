@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+import ladder_cases as lc
 import pfv_oracle_np as onp
 import pfv_oracle_entropy_np as oen
 import search_cases as sc
@@ -228,9 +229,10 @@ def check_shape(pkg, ctx, w, h, R, qualities=QUALITIES):
         enc.close()
 
 
-def _ipair(pkg, ctx, w, h, quality, first, make_second, R):
+def _ipair(pkg, ctx, w, h, quality, first, make_second, R, model_check=None):
     """i-frame `first`, then the p-frame make_second(padded reconstruction planes) in HIER mode at radius R: device == restatement at both
-    levels -> (mv, coarse vectors, has, restatement, planes)"""
+    levels -> (mv, coarse vectors, has, restatement, planes).  model_check(ref, planes, wmv, whas, wcoef): what a case asserts on the
+    restatement alone, before the device's p-frame is looked at"""
     enc = pkg.EncoderSession(ctx, w, h, quality, 1)
     ref = RefEncoder(w, h, quality)
     try:
@@ -240,9 +242,11 @@ def _ipair(pkg, ctx, w, h, quality, first, make_second, R):
         assert np.array_equal(enc.prev_frame()[0], ref.prev_frame())
         planes = [p.copy() for p in ref.prev]
         second = make_second(planes)
+        wmv, whas, wcoef = ref.pframe(second, R)
+        if model_check:
+            model_check(ref, planes, wmv, whas, wcoef)
         mv, has, coef = enc.encode_pframe(second)
         cmv = enc.coarse_vectors()
-        wmv, whas, wcoef = ref.pframe(second, R)
         assert np.array_equal(cmv[0], ref.cmv), np.nonzero((cmv[0] != ref.cmv).any(axis=1))[0][:8]
         assert np.array_equal(mv[0], wmv), np.nonzero((mv[0] != wmv).any(axis=1))[0][:8]
         assert np.array_equal(has[0], whas) and np.array_equal(coef[0], wcoef)
@@ -760,3 +764,69 @@ def check_time_tool(lib_path, w=64, h=48):
         assert all(v >= 0 for v in row[f"{key}_stages_ms"].values())            # the emulator's events read 0
     assert all(row[k] >= 0 for k in ("fourstep_ms", "full_r7_ms", "full_r15_ms"))
     return row
+
+
+# ------------------------------------------------------------------ 11. every even radius, the match in the corner of the square
+SWEEP_RADII = list(range(2, 63, 2))
+
+
+def check_sweep(pkg, ctx, R, w=sc.SWEEP_SHAPE[0], h=sc.SWEEP_SHAPE[1]):
+    """search_cases.check_sweep in HIER mode: the luma plane translated by (R, -R), then by (-R, R); the coarse vector of an inside
+    macroblock is (+-R / 2, -+R / 2), the corner of the coarse square, and the fine level keeps twice that.  Asserted on the restatement
+    first, then device == restatement at both levels (_ipair)."""
+    for dx, dy in ((R, -R), (-R, R)):
+        _ipair(pkg, ctx, w, h, sc.SWEEP_QUALITY, sc.sweep_first(w, h), lambda pl: pack(w, h, translate(pl[0], dx, dy), pl[1], pl[2]), R,
+               model_check=sc.corner_model_check(dx, dy, True))
+
+
+# ------------------------------------------------------------------ 12. ladder rungs
+LADDER_R = 30
+
+
+def hier_ladder_model(oracle, w, h, qualities, n=1, R=LADDER_R):
+    return sc.SearchLadderModel(oracle, w, h, qualities, n, lambda px, ref, q, px_err, clear: encode_plane_hier(px, ref, q, px_err, clear, R))
+
+
+def check_rate_rungs(pkg, ctx, oracle, device_entropy, R=LADDER_R, n_frames=8):
+    """pfv_encoder's rate controller moves the rung while HIER p-frames follow: the rungs the encoder reports are taken as they come, and the
+    stream's bytes equal the HIER ladder model's at those rungs (every p-frame payload at the rung that wrote it)"""
+    w, h = sc.LADDER_SHAPE
+    frames = lc.rate_clip(w, h)[:n_frames]
+    m = hier_ladder_model(oracle, w, h, lc.RATE_LADDER, 1, R)
+    m.iframe(0, frames[0], 2)
+    budget = int(1.25 * len(m.payload_p(*m.pframe(0, frames[1], 2), 2)))         # ladder_cases.rate_budget on the mode's model
+    plan = [("I", 2)] + [("P", None)] * (len(frames) - 1)
+    data, rungs = lc.run_encoder(pkg, ctx, w, h, frames, plan, device_entropy, qualities=lc.RATE_LADDER, rate=budget, search=("hier", R))
+    print(f"hier rate run: budget {budget}, rungs {rungs}")
+    assert min(rungs[1:]) > 0 and len(set(rungs[1:])) > 1, (rungs, "the controller never moved the rung")
+    model = hier_ladder_model(oracle, w, h, lc.RATE_LADDER, 1, R)
+    want, shown = lc.model_stream(model, frames, [(kind, rungs[t]) for t, (kind, _) in enumerate(plan)])
+    assert data == want, (len(data), len(want), rungs)
+    got, _ = lc.decode_both(pkg, ctx, oracle, data)
+    assert len(got) == len(shown) and all(np.array_equal(a, b) for a, b in zip(got, shown))
+
+
+# ------------------------------------------------------------------ 13. the largest error
+def check_largest(pkg, ctx, w=sc.LARGEST_SHAPE[0], h=sc.LARGEST_SHAPE[1], R=62):
+    """search_cases.check_largest in HIER mode: E = 256 x 255^2 at the fine level, 64 x 255^2 for every coarse candidate; both vectors are 0"""
+    for v in (0, 255):
+        first, second = sc.largest_frames(w, h, v)
+        _ipair(pkg, ctx, w, h, sc.SWEEP_QUALITY, first, lambda pl: second, R, model_check=sc.largest_model_check(w, h, True))
+
+
+# ------------------------------------------------------------------ 14. one pixel beyond the 7-bit field
+def check_field_edge(pkg, ctx, w=sc.SWEEP_SHAPE[0], h=sc.SWEEP_SHAPE[1], R=62):
+    """pans of (+-64, 0) and (0, +-64) at radius 62: the exact match is one pixel beyond |component| <= 63.  Of the restatement first: some
+    inside macroblock's coarse vector is +-31 along the pan and at most 1 across it, so the 25 vectors round twice of it hold the exact
+    match (E = 0) and only the rule's limit keeps it out; no vector component exceeds 63 and no inside macroblock carries the pan.  Then
+    device == restatement (_ipair).  (check_limits' pan of 64 at 160 x 96 has no such macroblock: profiles/search_mutants.md.)"""
+    for dx, dy in ((64, 0), (-64, 0), (0, 64), (0, -64)):
+        def model(ref, planes, wmv, whas, wcoef):
+            ins = sc.inside_blocks(planes[0].shape[1], planes[0].shape[0], dx, dy)
+            along, across = (0, 1) if dx else (1, 0)
+            c = ref.cmv[ins].astype(np.int64)
+            tempted = ins[(c[:, along] == (dx + dy) // 64 * 31) & (np.abs(c[:, across]) <= 1)]
+            assert tempted.size > 0, (dx, dy, c.tolist())
+            assert np.abs(wmv.astype(np.int64)).max() <= 63 and (ref.err[tempted] > 0).all()
+            assert not (wmv[ins] == np.array([dx, dy])).all(axis=1).any()
+        _ipair(pkg, ctx, w, h, sc.SWEEP_QUALITY, sc.sweep_first(w, h), lambda pl: pack(w, h, translate(pl[0], dx, dy), pl[1], pl[2]), R, model_check=model)

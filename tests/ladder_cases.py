@@ -292,12 +292,14 @@ def check_session_rungs(pkg, ctx, oracle, w, h, n, lane_mapping=None):
 
 
 # ------------------------------------------------------------------ check 3: the stream object
-def run_encoder(pkg, ctx, w, h, frames, plan, device_entropy, qualities=None, quality=None, rate=None):
-    """plan: per frame ('I' | 'P' | 'D', rung or None) -> (stream bytes, rung after every frame)"""
+def run_encoder(pkg, ctx, w, h, frames, plan, device_entropy, qualities=None, quality=None, rate=None, search=None):
+    """plan: per frame ('I' | 'P' | 'D', rung or None) -> (stream bytes, rung after every frame); search: (mode, radius) of set_motion_search"""
     buf = io.BytesIO()
     enc = pkg.Encoder(buf, w, h, 30, quality, ctx, device_entropy=device_entropy, qualities=qualities)
     rungs = []
     try:
+        if search:
+            enc.set_motion_search(*search)
         if rate:
             enc.set_rate(rate)
         for f, (kind, rung) in zip(frames, plan):

@@ -4,7 +4,8 @@ tests/test_emu_search.py on the CPU emulator build of the kernel sources and by 
 The expected values come from a numpy restatement of the rule in include/pfv_hip_ext.h ("exhaustive motion search"): every (dx, dy) of the
 square that stays inside the padded plane, exact integer SSD, the lexicographic minimum of (E, |dx| + |dy|, dy, dx) -- composed with the
 oracle's existing pieces (pad_plane, encode_plane / decode_plane, encode_blocks_delta, decode_plane_delta, qtables).  Every comparison is an
-equality."""
+equality.  Sections 9 .. 12 (every radius, ladder rungs, k_pf_transform's groups, the largest error) and what they kill:
+profiles/search_mutants.md."""
 import ctypes
 import io
 import json
@@ -15,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import ladder_cases as lc
 import pfv_oracle_np as onp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -293,8 +295,9 @@ def check_options(pkg, ctx, w=304, h=80, R=7, quality=2):
 
 
 # ------------------------------------------------------------------ 2. ties
-def _ipair(pkg, ctx, w, h, quality, first, make_second, R):
-    """i-frame `first`, then the p-frame make_second(padded reconstruction planes) in FULL mode at radius R -> (mv, has, restatement's, planes)"""
+def _ipair(pkg, ctx, w, h, quality, first, make_second, R, model_check=None):
+    """i-frame `first`, then the p-frame make_second(padded reconstruction planes) in FULL mode at radius R -> (mv, has, restatement's, planes).
+    model_check(ref, planes, wmv, whas, wcoef): what a case asserts on the restatement alone, before the device's p-frame is looked at"""
     enc = pkg.EncoderSession(ctx, w, h, quality, 1)
     ref = RefEncoder(w, h, quality)
     try:
@@ -304,8 +307,10 @@ def _ipair(pkg, ctx, w, h, quality, first, make_second, R):
         assert np.array_equal(enc.prev_frame()[0], ref.prev_frame())
         planes = [p.copy() for p in ref.prev]
         second = make_second(planes)
-        mv, has, coef = enc.encode_pframe(second)
         wmv, whas, wcoef = ref.pframe(second, R)
+        if model_check:
+            model_check(ref, planes, wmv, whas, wcoef)
+        mv, has, coef = enc.encode_pframe(second)
         assert np.array_equal(mv[0], wmv), np.nonzero((mv[0] != wmv).any(axis=1))[0][:8]
         assert np.array_equal(has[0], whas) and np.array_equal(coef[0], wcoef)
         assert np.array_equal(enc.prev_frame()[0], ref.prev_frame())
@@ -856,3 +861,246 @@ def check_time_tool(lib_path, w=64, h=48):
     row = json.loads(r.stdout.splitlines()[-1])["time_search"]
     assert row["streams"] == 2 and all(row[k] >= 0 for k in ("fourstep_ms", "full_r7_ms", "full_r15_ms"))      # the emulator's events read 0
     return row
+
+
+# ------------------------------------------------------------------ 9. every radius, the match in the corner of the square
+SWEEP_SHAPE = (144, 80)      # the smallest frame with two luma tiles across and two down: luma strips of 8 and of 1 macroblock, a partial
+SWEEP_SEED = 23              # 64-macroblock transform group, room for a +-62 vector
+SWEEP_QUALITY = 2
+SWEEP_RADII = list(range(1, 16))
+_SWEEP_FIRST = {}
+
+
+def sweep_first(w=SWEEP_SHAPE[0], h=SWEEP_SHAPE[1]):
+    if (w, h) not in _SWEEP_FIRST:
+        _SWEEP_FIRST[w, h] = moving_clip(w, h, 1, SWEEP_SEED, noise=0)[0]
+    return _SWEEP_FIRST[w, h]
+
+
+def inside_blocks(pw, ph, dx, dy):
+    """luma macroblocks of a pw x ph plane whose block displaced by (dx, dy) lies inside it"""
+    bw = pw // 16
+    return np.array([by * bw + bx for by in range(ph // 16) for bx in range(bw) if 0 <= bx * 16 + dx <= pw - 16 and 0 <= by * 16 + dy <= ph - 16], np.int64)
+
+
+def corner_model_check(dx, dy, coarse):
+    """of the restatement: every inside macroblock carries exactly (dx, dy) with E = 0 and has_coef = 0 (HIER: and the coarse vector
+    (dx / 2, dy / 2)), and there is one"""
+    def check(ref, planes, wmv, whas, wcoef):
+        ph, pw = planes[0].shape
+        ins = inside_blocks(pw, ph, dx, dy)
+        assert ins.size > 0, (dx, dy)
+        assert (wmv[ins] == np.array([dx, dy])).all(), (dx, dy, wmv[ins])
+        assert (ref.err[ins] == 0).all() and (whas[ins] == 0).all() and (wcoef[ins] == 0).all(), (dx, dy)
+        if coarse:
+            assert (ref.cmv[ins] == np.array([dx // 2, dy // 2])).all(), (dx, dy, ref.cmv[ins])
+    return check
+
+
+def check_sweep(pkg, ctx, R, w=SWEEP_SHAPE[0], h=SWEEP_SHAPE[1]):
+    """I then P at radius R: the p-frame is the i-frame's reconstruction with the luma plane translated by (R, -R), then by (-R, R) -- the
+    exact match is the corner candidate of the square, in the last column and the first row of the kernel's walk, then the first column
+    and the last row.  Asserted on the restatement first (corner_model_check), then device == restatement (_ipair)."""
+    for dx, dy in ((R, -R), (-R, R)):
+        _ipair(pkg, ctx, w, h, SWEEP_QUALITY, sweep_first(w, h), lambda pl: pack(w, h, translate(pl[0], dx, dy), pl[1], pl[2]), R,
+               model_check=corner_model_check(dx, dy, False))
+
+
+# ------------------------------------------------------------------ 10. ladder rungs
+LADDER_SHAPE = (50, 38)          # ladder_cases' own
+LADDER_R = 8
+LADDER_SESSION_PLAN = [("I", 3), ("P", 0), ("P", 4), ("P", 1)]      # the rung changes between p-frames: the reference plane is another rung's
+LADDER_ENCODER_PLAN = [("I", 3), ("P", 0), ("D", None), ("P", 4), ("I", 1), ("P", None), ("P", 2)]
+
+
+class SearchLadderModel(lc.LadderModel):
+    """ladder_cases.LadderModel with the p-frames of a motion-search mode: plane_encoder(px, ref, q, px_err, clear) -> (mv, has, coef, E, ...)
+    with the rung's inter tables and px_err.  .err[k]: E of the vectors of slot k's last p-frame"""
+
+    def __init__(self, oracle, w, h, qualities, n_streams=1, plane_encoder=None):
+        super().__init__(oracle, w, h, qualities, n_streams)
+        self.plane_encoder = plane_encoder
+        self.err = [None] * n_streams
+
+    def pframe(self, k, frame, rung):
+        el, ec, px_err = self.tabs[rung][2], self.tabs[rung][3], self.tabs[rung][4]
+        mvs, hass, coefs, recon, errs = [], [], [], [], []
+        for p, px in enumerate(lc.split(frame, self.w, self.h)):
+            q, ref = (el if p == 0 else ec), self.prev[k][p]
+            mv, has, c, err = self.plane_encoder(px, ref, q, px_err, self.CLEAR[p])[:4]
+            recon.append(self.o.decode_plane_delta(mv, has, c, ref.shape[1] // 16, ref.shape[0] // 16, q, ref))
+            mvs.append(mv); hass.append(has); coefs.append(c); errs.append(err)
+        self.prev[k] = recon
+        self.err[k] = np.concatenate(errs)
+        return np.concatenate(mvs), np.concatenate(hass), np.concatenate(coefs)
+
+    def has_at(self, k, rung):
+        """has_coef of the last p-frame of slot k had the skip threshold been `rung`'s (the vectors and E do not depend on it)"""
+        px_err = self.tabs[rung][4]
+        return (~(self.err[k].astype(np.float32) <= np.float32(px_err) * np.float32(px_err) * np.float32(256.0))).astype(np.uint8)
+
+
+def full_ladder_model(oracle, w, h, qualities, n=1, R=LADDER_R):
+    return SearchLadderModel(oracle, w, h, qualities, n, lambda px, ref, q, px_err, clear: encode_plane_full(px, ref, q, px_err, clear, R))
+
+
+def check_ladder_session(pkg, ctx, oracle, mode, R, make_model, n=3):
+    """I at rung 3, P at rung 0, P at rung 4, P at rung 1 of three streams in `mode`: mv, has_coef, coefficients, payloads and the next
+    reference equal the mode's ladder model at the rung of the frame.  Of the model first: at every rung > 0 some macroblock's has_coef is
+    not what rung 0's px_err would give -- else the case could not see a wrong skip threshold -- and some macroblock is coded."""
+    w, h = LADDER_SHAPE
+    model = make_model(oracle, w, h, lc.LADDER, n, R)
+    clips = [[f.copy() for f in lc.motion_clip(w, h, 11 + k, len(LADDER_SESSION_PLAN))] for k in range(n)]
+    rng = np.random.default_rng(17)
+    want = []
+    for t, (kind, rung) in enumerate(LADDER_SESSION_PLAN):
+        row = []
+        for k in range(n):
+            if t == len(LADDER_SESSION_PLAN) - 1:
+                # rung 0's px_err is 0 and rung 1's 3.0: the left 32 luma columns become the picture shown so far with noise of +-2, an
+                # error of about 2 per pixel, which rung 1 skips and rung 0 would code
+                y, shown = clips[k][t][:w * h].reshape(h, w), model.shown(k)[:w * h].reshape(h, w)
+                y[:, :32] = np.clip(shown[:, :32].astype(np.int64) + rng.integers(-2, 3, (h, 32)), 0, 255)
+            if kind == "I":
+                coef = model.iframe(k, clips[k][t], rung)
+                row.append((None, None, coef, model.payload_i(coef, rung), model.prev_frame(k), None))
+            else:
+                mv, has, coef = model.pframe(k, clips[k][t], rung)
+                row.append((mv, has, coef, model.payload_p(mv, has, coef, rung), model.prev_frame(k), model.has_at(k, 0)))
+        if kind == "P" and rung > 0:
+            assert any((r[1] != r[5]).any() for r in row), (t, rung, "rung 0's px_err gives the same has_coef")
+            assert any(r[1].any() for r in row), (t, rung, "nothing coded: the inter tables are not used")
+        want.append(row)
+    rig = lc.SessionRig(pkg, ctx, w, h, lc.LADDER, n)
+    try:
+        rig.enc.set_motion_search(mode, R)
+        for t, (kind, rung) in enumerate(LADDER_SESSION_PLAN):
+            got = rig.step(np.stack([clips[k][t] for k in range(n)]), kind == "P", rung)
+            assert rig.enc.rung == rung
+            for k in range(n):
+                mv, has, coef, pay, prev, _ = want[t][k]
+                if kind == "P":
+                    assert np.array_equal(got["mv"][k], mv), (t, k, "motion vectors")
+                    assert np.array_equal(got["has"][k], has), (t, k, "has_coef", np.nonzero(got["has"][k] != has)[0][:8])
+                assert np.array_equal(got["coef"][k], coef), (t, k, "coefficients")
+                assert np.array_equal(got["prev"][k], prev), (t, k, "reconstruction")
+                assert np.array_equal(rig.enc.prev_frame()[k], prev), (t, k, "prev_frame()")
+                assert got["payloads"][k] == pay, (t, k, len(got["payloads"][k]), len(pay))
+    finally:
+        rig.close()
+
+
+def check_ladder_encoder(pkg, ctx, oracle, mode, R, make_model, device_entropy):
+    """ladder_cases.check_encoder_ladder's plan through pfv_encoder in `mode`: the bytes are the mode's model's, both decoders show its frames"""
+    w, h = LADDER_SHAPE
+    plan = LADDER_ENCODER_PLAN
+    frames = lc.motion_clip(w, h, 41, len(plan))
+    data, rungs = lc.run_encoder(pkg, ctx, w, h, frames, plan, device_entropy, qualities=lc.LADDER, search=(mode, R))
+    assert rungs == [3, 0, 0, 4, 1, 1, 2]
+    full = [(kind, r if r is not None or kind == "D" else rungs[t]) for t, (kind, r) in enumerate(plan)]
+    model = make_model(oracle, w, h, lc.LADDER, 1, R)
+    want, shown = lc.model_stream(model, frames, full)
+    assert data == want, (len(data), len(want))
+    got, ofr = lc.decode_both(pkg, ctx, oracle, data)
+    assert len(ofr) == len(plan)
+    for t, (s, o) in enumerate(zip(shown, ofr)):
+        if s is not None:
+            assert o is not None and np.array_equal(o, s), t
+    delivered = [o for o in ofr if o is not None]
+    assert len(got) == len(delivered) and all(np.array_equal(a, b) for a, b in zip(got, delivered))
+
+
+# ------------------------------------------------------------------ 11. k_pf_transform's groups
+GROUPS_R = 4
+GROUPS_VECTOR = (3, -2)
+# 144 x 80: luma is 9 x 5 macroblocks in 10 strips (strip 2 by: 8 macroblocks, strip 2 by + 1: the one at bx = 8), k_pf_transform takes strips
+# 0 .. 7 (rows 0 .. 3) as group 0 and strips 8, 9 (row 4) as group 1; each 5 x 3 chroma plane is three strips in one group.  (by, bx):
+_G0_EIGHT = [(0, 0), (0, 7), (0, 8), (1, 2), (2, 8), (3, 0), (3, 7), (3, 8)]
+GROUP_SETS = {
+    "one": [(2, 3)],
+    "eight_in_group0": _G0_EIGHT,
+    "nine_in_group0": _G0_EIGHT + [(1, 5)],
+    "one_macroblock_strips": [(by, 8) for by in range(5)],
+    "group1_only": [(4, bx) for bx in range(9)],
+    "all": "all",
+}
+
+
+def groups_second(planes, w, h, name):
+    """-> (the p-frame, the macroblocks that must come out coded).  Every luma macroblock's source is the reconstruction's patch displaced by
+    (3, -2) -- where that leaves the plane (the top row, the right column) the component is clamped to 0, a plain translation would leave
+    those 13 macroblocks without an exact match -- and chroma is the reconstruction: nothing is coded.  Then the macroblocks of the set
+    become random bytes."""
+    y = planes[0].copy()
+    ph, pw = y.shape
+    bw = pw // 16
+    for by in range(ph // 16):
+        for bx in range(bw):
+            vx, vy = min(GROUPS_VECTOR[0], pw - 16 - bx * 16), max(GROUPS_VECTOR[1], -by * 16)
+            y[by * 16:by * 16 + 16, bx * 16:bx * 16 + 16] = planes[0][by * 16 + vy:by * 16 + vy + 16, bx * 16 + vx:bx * 16 + vx + 16]
+    rng = np.random.default_rng(77)
+    nl = bw * (ph // 16)
+    if GROUP_SETS[name] == "all":
+        f = rng.integers(0, 256, frame_bytes(w, h), dtype=np.uint8)
+        return f, np.arange(nl + 2 * (planes[1].shape[0] // 16) * (planes[1].shape[1] // 16))
+    for by, bx in GROUP_SETS[name]:
+        y[by * 16:by * 16 + 16, bx * 16:bx * 16 + 16] = rng.integers(0, 256, (16, 16), dtype=np.uint8)
+    return pack(w, h, y, planes[1], planes[2]), np.array(sorted(by * bw + bx for by, bx in GROUP_SETS[name]))
+
+
+def check_groups(pkg, ctx, name, transform, w=SWEEP_SHAPE[0], h=SWEEP_SHAPE[1]):
+    """FULL at radius 4 under PFV_OPT_ENC_TRANSFORM = transform.  Of the restatement: exactly the chosen set is coded, an uncoded
+    macroblock's coefficients are zero and its reconstruction is the displaced patch; then device == restatement (_ipair), so the same
+    holds of the device's outputs."""
+    opt = pkg._lib.PFV_OPT_ENC_TRANSFORM
+    chosen = {}
+
+    def second(planes):
+        f, chosen["set"] = groups_second(planes, w, h, name)
+        return f
+
+    def model(ref, planes, wmv, whas, wcoef):
+        assert np.array_equal(np.nonzero(whas)[0], chosen["set"]), (name, np.nonzero(whas)[0], chosen["set"])
+        assert (wcoef[whas == 0] == 0).all() and (np.abs(wcoef[whas == 1]).sum(axis=1) > 0).all()
+        off = 0
+        for before, after in zip(planes, ref.prev):
+            bw, bh = before.shape[1] // 16, before.shape[0] // 16
+            for i in range(bw * bh):
+                if not whas[off + i]:
+                    bx, by, (vx, vy) = (i % bw) * 16, (i // bw) * 16, (int(v) for v in wmv[off + i])
+                    assert np.array_equal(after[by:by + 16, bx:bx + 16], before[by + vy:by + vy + 16, bx + vx:bx + vx + 16]), (name, off + i)
+            off += bw * bh
+    before = ctx.get_option(opt)
+    ctx.set_option(opt, transform)
+    try:
+        _ipair(pkg, ctx, w, h, SWEEP_QUALITY, sweep_first(w, h), second, GROUPS_R, model_check=model)
+    finally:
+        ctx.set_option(opt, before)
+
+
+# ------------------------------------------------------------------ 12. the largest error
+LARGEST_SHAPE = (48, 32)
+LARGEST_E = 256 * 255 * 255          # one short step below 2^24: the headroom of the 64-bit keys and the u32 sums
+
+
+def largest_frames(w, h, first_value):
+    grey = np.full((h, w), 128, np.uint8)
+    return [pack(w, h, np.full((h, w), v, np.uint8), grey, grey) for v in (first_value, 255 - first_value)]
+
+
+def largest_model_check(w, h, coarse):
+    def check(ref, planes, wmv, whas, wcoef):
+        nl = (w // 16) * (h // 16)
+        assert all((p == p.flat[0]).all() for p in planes) and planes[0].flat[0] in (0, 255), "the reconstruction is not flat"
+        assert (ref.err[:nl] == LARGEST_E).all() and LARGEST_E < 1 << 24, ref.err     # flat against flat: E of every candidate
+        assert (wmv == 0).all() and (whas[:nl] == 1).all() and (whas[nl:] == 0).all()
+        if coarse:
+            assert (ref.cmv == 0).all()
+    return check
+
+
+def check_largest(pkg, ctx, w=LARGEST_SHAPE[0], h=LARGEST_SHAPE[1], R=15):
+    """luma all 0 then all 255, and the other way round: every candidate of every luma macroblock has E = 256 x 255^2, (0, 0) wins, all are coded"""
+    for v in (0, 255):
+        first, second = largest_frames(w, h, v)
+        _ipair(pkg, ctx, w, h, SWEEP_QUALITY, first, lambda pl: second, R, model_check=largest_model_check(w, h, False))

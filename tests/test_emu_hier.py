@@ -4,6 +4,7 @@ tests/hier_cases.py, every one an equality with the numpy restatement of the hea
 import pytest
 
 import hier_cases as hc
+import search_cases as sc
 
 
 @pytest.mark.parametrize("R", hc.RADII)
@@ -56,3 +57,30 @@ def test_emu_hier_rd_tool(pkg, emu_ctx):
     import conftest
     hc.check_rd_tool(conftest.build_emulator())
     hc.check_time_tool(conftest.build_emulator())
+
+
+@pytest.mark.parametrize("R", hc.SWEEP_RADII)
+def test_emu_hier_sweep(pkg, emu_ctx, R):
+    hc.check_sweep(pkg, emu_ctx, R)
+
+
+def test_emu_hier_ladder_session(pkg, emu_ctx, oracle):
+    sc.check_ladder_session(pkg, emu_ctx, oracle, "hier", hc.LADDER_R, hc.hier_ladder_model)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_emu_hier_ladder_encoder(pkg, emu_ctx, oracle, device_entropy):
+    sc.check_ladder_encoder(pkg, emu_ctx, oracle, "hier", hc.LADDER_R, hc.hier_ladder_model, device_entropy)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_emu_hier_rate_rungs(pkg, emu_ctx, oracle, device_entropy):
+    hc.check_rate_rungs(pkg, emu_ctx, oracle, device_entropy)
+
+
+def test_emu_hier_largest(pkg, emu_ctx):
+    hc.check_largest(pkg, emu_ctx)
+
+
+def test_emu_hier_field_edge(pkg, emu_ctx):
+    hc.check_field_edge(pkg, emu_ctx)

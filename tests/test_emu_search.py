@@ -56,3 +56,27 @@ def test_emu_search_rd_tool(pkg, emu_ctx, tmp_path):
     import conftest
     sc.check_rd_tool(pkg, conftest.build_emulator(), tmp_path)
     sc.check_time_tool(conftest.build_emulator())
+
+
+@pytest.mark.parametrize("R", sc.SWEEP_RADII)
+def test_emu_search_sweep(pkg, emu_ctx, R):
+    sc.check_sweep(pkg, emu_ctx, R)
+
+
+def test_emu_search_ladder_session(pkg, emu_ctx, oracle):
+    sc.check_ladder_session(pkg, emu_ctx, oracle, "full", sc.LADDER_R, sc.full_ladder_model)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_emu_search_ladder_encoder(pkg, emu_ctx, oracle, device_entropy):
+    sc.check_ladder_encoder(pkg, emu_ctx, oracle, "full", sc.LADDER_R, sc.full_ladder_model, device_entropy)
+
+
+@pytest.mark.parametrize("transform", [0, 1])
+@pytest.mark.parametrize("name", list(sc.GROUP_SETS))
+def test_emu_search_groups(pkg, emu_ctx, name, transform):
+    sc.check_groups(pkg, emu_ctx, name, transform)
+
+
+def test_emu_search_largest(pkg, emu_ctx):
+    sc.check_largest(pkg, emu_ctx)

@@ -4,6 +4,7 @@ the emulator twin (tests/test_emu_hier.py), every one an equality with the numpy
 import pytest
 
 import hier_cases as hc
+import search_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -65,3 +66,30 @@ def test_gpu_hier_cpp_mirror(graft, pkg, gpu_ctx, tmp_path):
 def test_gpu_hier_rd_tool(graft, pkg, gpu_ctx):
     hc.check_rd_tool(_lib(graft))
     hc.check_time_tool(_lib(graft))
+
+
+@pytest.mark.parametrize("R", hc.SWEEP_RADII)
+def test_gpu_hier_sweep(pkg, gpu_ctx, R):
+    hc.check_sweep(pkg, gpu_ctx, R)
+
+
+def test_gpu_hier_ladder_session(pkg, gpu_ctx, oracle):
+    sc.check_ladder_session(pkg, gpu_ctx, oracle, "hier", hc.LADDER_R, hc.hier_ladder_model)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_gpu_hier_ladder_encoder(pkg, gpu_ctx, oracle, device_entropy):
+    sc.check_ladder_encoder(pkg, gpu_ctx, oracle, "hier", hc.LADDER_R, hc.hier_ladder_model, device_entropy)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_gpu_hier_rate_rungs(pkg, gpu_ctx, oracle, device_entropy):
+    hc.check_rate_rungs(pkg, gpu_ctx, oracle, device_entropy)
+
+
+def test_gpu_hier_largest(pkg, gpu_ctx):
+    hc.check_largest(pkg, gpu_ctx)
+
+
+def test_gpu_hier_field_edge(pkg, gpu_ctx):
+    hc.check_field_edge(pkg, gpu_ctx)

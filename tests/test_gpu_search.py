@@ -65,3 +65,27 @@ def test_gpu_search_cpp_mirror(graft, pkg, gpu_ctx, tmp_path):
 def test_gpu_search_rd_tool(graft, pkg, gpu_ctx, tmp_path):
     sc.check_rd_tool(pkg, _lib(graft), tmp_path)
     sc.check_time_tool(_lib(graft))
+
+
+@pytest.mark.parametrize("R", sc.SWEEP_RADII)
+def test_gpu_search_sweep(pkg, gpu_ctx, R):
+    sc.check_sweep(pkg, gpu_ctx, R)
+
+
+def test_gpu_search_ladder_session(pkg, gpu_ctx, oracle):
+    sc.check_ladder_session(pkg, gpu_ctx, oracle, "full", sc.LADDER_R, sc.full_ladder_model)
+
+
+@pytest.mark.parametrize("device_entropy", [False, True])
+def test_gpu_search_ladder_encoder(pkg, gpu_ctx, oracle, device_entropy):
+    sc.check_ladder_encoder(pkg, gpu_ctx, oracle, "full", sc.LADDER_R, sc.full_ladder_model, device_entropy)
+
+
+@pytest.mark.parametrize("transform", [0, 1])
+@pytest.mark.parametrize("name", list(sc.GROUP_SETS))
+def test_gpu_search_groups(pkg, gpu_ctx, name, transform):
+    sc.check_groups(pkg, gpu_ctx, name, transform)
+
+
+def test_gpu_search_largest(pkg, gpu_ctx):
+    sc.check_largest(pkg, gpu_ctx)
