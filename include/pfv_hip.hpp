@@ -254,6 +254,66 @@ inline std::vector<uint8_t> frames_denoise(Context &ctx, size_t width, size_t he
     return out;
 }
 
+// pfv_scene_stats (pfv_hip_ext.h, "scene-cut detection") of one pair of frames, with the score the host functions make of it
+struct SceneStats : pfv_scene_stats {
+    SceneStats() : pfv_scene_stats{} {}
+    SceneStats(const pfv_scene_stats &s) : pfv_scene_stats(s) {}
+    uint32_t score_q8() const { return pfv_scene_score_q8(this); }
+};
+// frame types (1 i-frame, 2 p-frame) for the frames the stats describe (pfv_scene_plan)
+inline std::vector<uint8_t> scene_plan(const std::vector<SceneStats> &stats, uint32_t threshold_q8 = PFV_SCENE_THRESHOLD_DEFAULT, int min_interval = 0, int max_interval = 0)
+{
+    static_assert(sizeof(SceneStats) == sizeof(pfv_scene_stats), "SceneStats adds no member");
+    std::vector<uint8_t> types(stats.size());
+    if (pfv_scene_plan(stats.data(), (int)stats.size(), threshold_q8, min_interval, max_interval, types.data()) < 0) throw std::invalid_argument("scene_plan: bad argument");
+    return types;
+}
+// pfv_scene_detector: the previous quarter plane and the primed flag of n_streams streams; destroy it before its context
+class SceneDetector {
+  public:
+    SceneDetector(Context &ctx, size_t width, size_t height, int n_streams = 1, int max_clip_frames = 0) : ctx_(ctx), width_(width), height_(height), n_(n_streams)
+    {
+        int rc = PFV_OK;
+        h_ = pfv_scene_detector_create(ctx.handle(), (int)width, (int)height, n_streams, max_clip_frames, &rc);
+        if (!h_) ctx_.check(rc ? rc : PFV_ERR_BAD_ARG);
+    }
+    ~SceneDetector() { pfv_scene_detector_destroy(h_); }
+    SceneDetector(const SceneDetector &) = delete;
+    SceneDetector &operator=(const SceneDetector &) = delete;
+    pfv_scene_detector *handle() const { return h_; }
+    size_t frame_bytes() const { return pfv_frame_bytes((int)width_, (int)height_); }
+    size_t n_blocks() const { return ((width_ >> 2) >> 3) * ((height_ >> 2) >> 3); }
+    // R in quarter samples, 0 .. 7, for the runs that follow
+    void set_radius(int radius) { ctx_.check(pfv_scene_detector_set_radius(h_, radius)); }
+    void reset(int first_stream = 0, int n = -1) { ctx_.check(pfv_scene_detector_reset(h_, first_stream, n < 0 ? n_ - first_stream : n)); }
+    // asynchronous on the context's stream, one launch group: device frames in (packed or padded, src_stride apart), n stats in device memory out
+    void run_dev(int first_stream, int n, const uint8_t *src_dev, pfv_scene_stats *stats_dev, bool commit = true, int src_layout = PFV_FRAME_PACKED, size_t src_stride = 0)
+    {
+        ctx_.check(pfv_scene_detector_run_dev(h_, first_stream, n, src_dev, src_layout, src_stride, commit ? 1 : 0, stats_dev));
+    }
+    // n_frames consecutive frames of one stream, the first against the stream's state
+    void run_clip_dev(int stream, int n_frames, const uint8_t *frames_dev, pfv_scene_stats *stats_dev, bool commit = true, int layout = PFV_FRAME_PACKED, size_t stride = 0)
+    {
+        ctx_.check(pfv_scene_detector_run_clip_dev(h_, stream, n_frames, frames_dev, layout, stride, commit ? 1 : 0, stats_dev));
+    }
+
+  private:
+    Context &ctx_;
+    size_t width_, height_;
+    int n_;
+    pfv_scene_detector *h_ = nullptr;
+};
+// packed frames, frame-major ([frame][stream]), through a fresh detector in order: [frame][stream] stats
+inline std::vector<SceneStats> frames_scene(Context &ctx, size_t width, size_t height, const std::vector<uint8_t> &frames, int radius = PFV_SCENE_RADIUS_DEFAULT, int n_streams = 1)
+{
+    const size_t fb = pfv_frame_bytes((int)width, (int)height);
+    if (!fb || n_streams <= 0 || frames.empty() || frames.size() % (fb * (size_t)n_streams)) throw std::invalid_argument("frames_scene: frames must hold whole packed frames of every stream");
+    const size_t n_frames = frames.size() / (fb * (size_t)n_streams);
+    std::vector<SceneStats> out(n_frames * (size_t)n_streams);
+    ctx.check(pfv_frames_scene(ctx.handle(), (int)width, (int)height, n_streams, (int)n_frames, frames.data(), radius, out.data()));
+    return out;
+}
+
 // motion search of an encoder session and of the stream encoders over it (pfv_*_set_motion_search): FourStep is the reference's search
 enum class MotionSearch { FourStep = PFV_SEARCH_FOURSTEP, Full = PFV_SEARCH_FULL, Hier = PFV_SEARCH_HIER };
 
@@ -497,6 +557,19 @@ class Encoder {
     void set_pframe_probe(bool on) { ctx_.check(pfv_encoder_set_pframe_probe(h_, on ? 1 : 0)); }
     // encode_frame forces an i-frame once max_interval frames (drop frames included) have followed the last one; 0 = never
     void set_gop(int max_interval) { ctx_.check(pfv_encoder_set_gop(h_, max_interval)); }
+    // scene-cut detection on the staged frame of every encode_* (committed) and probe_* (uncommitted) call; encode_frame then writes an i-frame
+    // where the score reaches threshold_q8 and min_interval frames have followed the last one, in every search mode (pfv_encoder_set_scene_cut)
+    void set_scene_cut(bool on, uint32_t threshold_q8 = PFV_SCENE_THRESHOLD_DEFAULT, int radius = PFV_SCENE_RADIUS_DEFAULT, int min_interval = 0)
+    {
+        ctx_.check(pfv_encoder_set_scene_cut(h_, on ? 1 : 0, threshold_q8, radius, min_interval));
+    }
+    // the stats of the last call that measured a frame; pfv::Error(PFV_ERR_STATE) when the switch is off or nothing has been measured
+    SceneStats last_scene() const
+    {
+        pfv_scene_stats s;
+        ctx_.check(pfv_encoder_last_scene(h_, &s));
+        return SceneStats(s);
+    }
     // the frame's type chosen by the probes (pfv_encoder_encode_frame) -> 1 i-frame, 2 p-frame, 3 drop frame
     int encode_frame(const VideoFrame &f)
     {

@@ -827,7 +827,8 @@ PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on);
  * Costs per frame behind the first: up to two launch pairs, two downloads of at most 84 * n_rungs and 4 * n_rungs bytes, each with its
  * synchronisation, before the encode itself.  Rule 4 means what it says and is NOT a scene-cut detector: residuals are halved
  * (src/common.rs:118-119, :304), so a p-frame across a cut is often the smaller one (texture, noise) and is then written.  Frame reports
- * work as for the explicit calls.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have none of this.
+ * work as for the explicit calls.  pfv_gop_encoder and pfv_batch_encoder keep one quality and have none of this.  The detector is a switch
+ * of its own, pfv_encoder_set_scene_cut ("scene-cut detection", below): it adds rule 1b and serves the other two objects as a look-ahead.
  *   4 with the p-frame quality floor on (pfv_encoder_set_pframe_quality_floor, below; rules 1 to 3 stay, rp = the floor's rung): the frame is
  *      measured as an i-frame by the rate-distortion probe from the same upload; ri = the rung encode_iframe would choose with its own budget and
  *      floor settings, from these results (no second probe, no second upload).  The candidates are the p-frame at rp and the i-frame at ri; each
@@ -836,6 +837,94 @@ PFV_API int pfv_encoder_set_pframe_probe(pfv_encoder *e, int on);
  *      not encodable never meets and loses to one that is.  The i-frame is written at ri, the p-frame at rp; either becomes the current rung. */
 PFV_API int pfv_encoder_set_gop(pfv_encoder *e, int max_interval);
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out /* 1 i, 2 p, 3 drop */);
+
+/* ------------------------------------------------------------------ scene-cut detection  [B]
+ * A cheap look-ahead measure between "frames in HBM" and "which of them start a GOP": how well the previous frame predicts this one, against how
+ * much this one varies in itself.  A zero-motion difference is not enough (a pan scores like a cut), so the measure holds a small motion
+ * search at quarter resolution.  Integer, order-free, many frames or streams per launch.  Fades, flashes and chroma are out of scope.
+ *
+ * The measure (normative).  Luma only; `prev` and `cur` are two frames of w x h; everything is exact integer arithmetic.
+ *   Quarter planes.  qw = w >> 2, qh = h >> 2.  Q[y][x] = (sum of the 4 x 4 luma pixels at (4x, 4y) + 8) >> 4.  Pixels beyond 4 qw / 4 qh and
+ *                    any padding never take part.
+ *   Blocks.          nbx = qw >> 3, nby = qh >> 3 blocks of 8 x 8 quarter samples (32 x 32 pixels).  Quarter samples beyond 8 nbx / 8 nby belong
+ *                    to no block as the CURRENT block, but a candidate may cover them.  n_blocks = nbx * nby may be 0.
+ *   Intra.           Per block B of Qcur at (8bx, 8by): mean = (sum B + 32) >> 6, intra = sum |B - mean|  (<= 16 320).
+ *   Inter.           The candidates are all (cx, cy) with |cx|, |cy| <= R, 0 <= 8bx + cx <= qw - 8 and 0 <= 8by + cy <= qh - 8.  S(cx, cy) is the
+ *                    SAD of B against the 8 x 8 block of Qprev at (8bx + cx, 8by + cy).  The chosen candidate is the lexicographic minimum of
+ *                    (S, |cx| + |cy|, cy, cx) -- the project's tie rule.  best = S(chosen), zero = S(0, 0).  The radius R is 0 .. 7 quarter
+ *                    samples (+-4R pixels); the default 4 matches the four-step search's +-15; R = 0 is zero motion only.
+ *   Per pair of frames, pfv_scene_stats (40 bytes): inter = sum best, intra = sum intra, zero = sum zero over the blocks; n_blocks (0 when the
+ *                    stream has no previous frame: every other field is then 0 too); n_intra = blocks with best >= intra; n_moving = blocks
+ *                    whose chosen vector is not (0, 0); reserved = 0.  Every entry is written by every run: no atomics, nothing to clear.
+ *   Per block maps (diagnostics, [C]): uint32 best << 16 | intra, and int8[2] = the chosen (cx, cy).
+ * Three kernels (csrc/pfv_scene_kernels.hip): k_scene_quarter (frames -> u8 quarter planes; PACKED or PADDED operand with its own stream stride,
+ * 16-byte loads where legal and a byte path with the same result otherwise), k_scene_cost (one wavefront per block, the window of Qprev in LDS,
+ * one lane per candidate, v_sad_u8, the tie rule as the minimum of one packed key) and k_scene_sum (the map summed per pair, 64-bit).  Measured
+ * on one MI355X: profiles/scene_cut.md. */
+typedef struct pfv_scene_stats {
+    uint64_t inter, intra, zero;
+    uint32_t n_blocks, n_intra, n_moving, reserved;
+} pfv_scene_stats;
+enum { PFV_SCENE_RADIUS_DEFAULT = 4, PFV_SCENE_THRESHOLD_DEFAULT = 176 };
+/* Pure host functions.  The score in q8: 0 when n_blocks == 0, else min(65535, inter * 256 / max(intra, 64 * n_blocks)), floor division; the
+ * 64 * n_blocks floor keeps flat or black frames from dividing by nothing (black -> black is 0, black <-> picture is large).  The default
+ * threshold 176 is the geometric mean of the largest continuous score and the smallest cut score of synthetic clips at R = 5
+ * (profiles/scene_cut.md); nobody has measured real footage, and the threshold is the caller's argument. */
+PFV_API uint32_t pfv_scene_score_q8(const pfv_scene_stats *stats);
+/* types_out[k] = 1 (i-frame) or 2 (p-frame) for stats[0 .. n_frames), returns the number of i-frames.  Frame 0 is an i-frame.  With d = k - (the
+ * index of the last i-frame): frame k is an i-frame when max_interval > 0 && d >= max_interval, or when score(stats[k]) >= threshold_q8 &&
+ * d >= max(1, min_interval); every other frame is a p-frame.  Null pointers, n_frames <= 0 or a negative interval: PFV_ERR_BAD_ARG. */
+PFV_API int pfv_scene_plan(const pfv_scene_stats *stats, int n_frames, uint32_t threshold_q8, int min_interval, int max_interval, uint8_t *types_out);
+/* The detector owns, per stream, the previous quarter plane (the state) and a `primed` flag in device memory (handled as pfv_denoiser handles
+ * its own: create and reset clear them with stream-ordered memsets, a committed run over an unprimed stream sets its window's flags with a
+ * memset behind the kernels), quarter scratch for max(n_streams, max_clip_frames) frames and the block maps.  Width and height positive, even,
+ * <= 65535; n_streams >= 1; max_clip_frames >= 0.  NULL and *err on failure (err may be NULL); PFV_ERR_STATE inside a graph recording.  Destroy
+ * it before its context. */
+typedef struct pfv_scene_detector pfv_scene_detector;
+PFV_API pfv_scene_detector *pfv_scene_detector_create(pfv_ctx *ctx, int width, int height, int n_streams, int max_clip_frames, int *err);
+PFV_API void pfv_scene_detector_destroy(pfv_scene_detector *det);
+/* R for the runs that follow; outside 0 .. 7: PFV_ERR_BAD_ARG and the radius stays as it was */
+PFV_API int pfv_scene_detector_set_radius(pfv_scene_detector *det, int radius);
+/* un-primes streams [first_stream, first_stream + n); stream-ordered */
+PFV_API int pfv_scene_detector_reset(pfv_scene_detector *det, int first_stream, int n);
+/* Frame t of streams [first_stream, first_stream + n) in one launch group (three kernels), asynchronous on the context's stream: stream
+ * first_stream + k's frame is at src_dev + k * src_stride (0 = back to back in the layout) and is measured against that stream's state into
+ * stats_dev[k] (device memory, 8-byte aligned).  Streams outside the window are left alone.  With commit the current quarter planes become the
+ * state through a stream-ordered copy and the streams are primed; an uncommitted run leaves state and priming alone.  A steady-state run is
+ * recordable; a run that must set `primed` flags inside a graph recording returns PFV_ERR_STATE.  PFV_ERR_BAD_ARG: a null pointer, a window
+ * outside n_streams, a layout that does not exist, a stride below the layout's frame size, a misaligned stats_dev -- nothing is written. */
+PFV_API int pfv_scene_detector_run_dev(pfv_scene_detector *det, int first_stream, int n, const uint8_t *src_dev, int src_layout, size_t src_stride, int commit,
+                                       pfv_scene_stats *stats_dev /*[n]*/);
+/* n_frames <= max_clip_frames consecutive frames of ONE stream, frame k at frames_dev + k * stride, in one launch group: entry 0 is measured
+ * against the stream's state, entry k against frame k - 1; with commit the last frame becomes the state.  The results are bit for bit those of
+ * n_frames committed run_dev calls on that stream.  The recipe for pfv_gop_encoder, which needs its GOP boundaries before anything is encoded:
+ * measure the clip in HBM once, pfv_scene_plan, then feed pfv_gop_encoder_encode_iframe_dev / _pframe_dev by the plan. */
+PFV_API int pfv_scene_detector_run_clip_dev(pfv_scene_detector *det, int stream, int n_frames, const uint8_t *frames_dev, int layout, size_t stride, int commit,
+                                            pfv_scene_stats *stats_dev /*[n_frames]*/);
+/* [C] the block maps of the last run, entries [first, first + n) -- run_dev: stream indices, run_clip_dev: frame indices -- each
+ * n_blocks = ((w >> 2) >> 3) * ((h >> 2) >> 3) long; either pointer may be NULL; waits for the stream */
+PFV_API int pfv_scene_detector_maps(pfv_scene_detector *det, int first, int n, uint32_t *blk_out, int8_t *vec_out);
+/* [C] measurement only: an UNCOMMITTED run_dev (clip == 0: streams [first, first + n)) or run_clip_dev (clip != 0: n frames of stream `first`)
+ * with an event between the kernels; synchronises.  ms_out: k_scene_quarter, k_scene_cost, k_scene_sum.  PFV_ERR_STATE inside a graph recording. */
+PFV_API int pfv_scene_detector_run_timed_dev(pfv_scene_detector *det, int first, int n, int clip, const uint8_t *src_dev, int layout, size_t stride,
+                                             pfv_scene_stats *stats_dev, float ms_out[3]);
+/* host frames, packed, frame-major ([frame][stream]): makes a detector, runs the frames in order, committed, and synchronises; stats_out
+ * [n_frames][n_streams]; the mirror of pfv_frames_denoise.  PFV_ERR_STATE while a graph is being recorded */
+PFV_API int pfv_frames_scene(pfv_ctx *ctx, int width, int height, int n_streams, int n_frames, const uint8_t *frames, int radius, pfv_scene_stats *stats_out);
+/* pfv_encoder: cut-aware frame types.  The detector (one stream, owned) and its scratch are made by this call, never by an encode call; radius
+ * 0 .. 7 and min_interval >= 0, else PFV_ERR_BAD_ARG; switching on (from off) un-primes the detector.
+ * ON: every encode_iframe / encode_pframe / encode_frame call measures the STAGED frame (behind ingest -> scale -> denoise) committed, once per
+ * call; the six pfv_encoder_probe_* calls measure uncommitted; encode_dropframe leaves the state alone.  The frame goes up once per call.
+ * pfv_encoder_encode_frame gains rule 1b between rules 1 and 2: score >= threshold_q8 and at least max(1, min_interval) frames, drop frames
+ * included, have followed the last i-frame, this frame counted (d of pfv_scene_plan: an i-frame directly behind an i-frame is possible unless
+ * min_interval >= 2): an i-frame, its rung chosen as encode_iframe chooses it; no p-frame sizing runs.  Otherwise rules 2 - 5 apply as they are.  With PFV_SEARCH_FULL / PFV_SEARCH_HIER and the switch on, encode_frame no longer
+ * returns PFV_ERR_STATE: rule 1, rule 1b, else a p-frame at the current rung -- no sizing, no drop frames.  Costs one launch group, one 40-byte
+ * download and one synchronisation per frame.
+ * OFF (the default, or after on = 0): no launch, no byte and no return code differs from an encoder without the switch, PFV_ERR_STATE from
+ * encode_frame in FULL / HIER mode included. */
+PFV_API int pfv_encoder_set_scene_cut(pfv_encoder *e, int on, uint32_t threshold_q8, int radius, int min_interval);
+/* the stats of the last call that measured; PFV_ERR_STATE when the switch is off or no frame has been measured */
+PFV_API int pfv_encoder_last_scene(pfv_encoder *e, pfv_scene_stats *out);
 
 /* ------------------------------------------------------------------ p-frame rate-distortion probe, p-frame quality floor  [B]
  * A p-frame is often the smaller frame AND the worse-looking one: residuals are halved, and a skipped macroblock costs no bytes whatever its
@@ -982,7 +1071,10 @@ PFV_API void pfv_batch_decoder_destroy(pfv_batch_decoder *b);
  * stream order, with the results (1 / 0 / error) the sequential loop gives call by call -- a packet that does not parse leaves
  * the framebuffer alone, and the frames behind a failed i-frame decode against the previous run's last frame, as they do there.
  * y / u / v of the callback are one packed frame (u == y + w*h, v == u + (w/2)*(h/2)) and stay valid until the call that starts
- * the next batch. */
+ * the next batch.
+ * GOP boundaries: the encoder runs one stream's GOPs side by side, so they must be known before anything is encoded; it has no switch for
+ * that.  The recipe: measure the clip where it lies in HBM with pfv_scene_detector_run_clip_dev, turn the stats into frame types with
+ * pfv_scene_plan (a fixed interval is its max_interval), and feed encode_iframe_dev / encode_pframe_dev by the plan. */
 typedef struct pfv_gop_encoder pfv_gop_encoder;
 typedef struct pfv_gop_decoder pfv_gop_decoder;
 typedef struct pfv_iovec { const uint8_t *data; size_t len; } pfv_iovec;

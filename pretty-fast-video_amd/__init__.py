@@ -20,6 +20,7 @@ from .dec import BatchDecoder, Decoder, DecodeError, GopDecoder
 from .synth import SyntheticStream
 from .scale import Scaler, frames_scale, scale_table, scale_taps
 from .denoise import Denoiser, frames_denoise
+from .scene import SceneDetector, SceneStats, frames_scene, scene_plan, scene_score
 from .quality import FrameReport, FrameSsim, deblock_strength, frames_deblock, frames_from_rgb, frames_sse, frames_to_rgb, frames_ssim, psnr, ssim, ssim_windows
 
 __all__ = ["Context", "Graph", "VideoPlane", "VideoFrame", "EncodedIPlane", "EncodedPPlane", "EncoderSession",

@@ -212,6 +212,19 @@ SIGNATURES = [
     ("pfv_frames_denoise", c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     ("pfv_enc_denoise_dev", c_int, [_P, _P, _P, c_size_t, c_int, _P]),
     ("pfv_encoder_set_denoise", c_int, [_P, c_int, _P, _P]),
+    ("pfv_scene_score_q8", ctypes.c_uint32, [_P]),
+    ("pfv_scene_plan", c_int, [_P, c_int, ctypes.c_uint32, c_int, c_int, _P]),
+    ("pfv_scene_detector_create", _P, [_P, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    ("pfv_scene_detector_destroy", None, [_P]),
+    ("pfv_scene_detector_set_radius", c_int, [_P, c_int]),
+    ("pfv_scene_detector_reset", c_int, [_P, c_int, c_int]),
+    ("pfv_scene_detector_run_dev", c_int, [_P, c_int, c_int, _P, c_int, c_size_t, c_int, _P]),
+    ("pfv_scene_detector_run_clip_dev", c_int, [_P, c_int, c_int, _P, c_int, c_size_t, c_int, _P]),
+    ("pfv_scene_detector_maps", c_int, [_P, c_int, c_int, _P, _P]),
+    ("pfv_scene_detector_run_timed_dev", c_int, [_P, c_int, c_int, c_int, _P, c_int, c_size_t, _P, _P]),
+    ("pfv_frames_scene", c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    ("pfv_encoder_set_scene_cut", c_int, [_P, c_int, ctypes.c_uint32, c_int, c_int]),
+    ("pfv_encoder_last_scene", c_int, [_P, _P]),
     ("pfv_enc_session_create_ladder", c_int, [_P, c_int, c_int, _P, c_int, c_int, POINTER(_P)]),
     ("pfv_enc_session_set_motion_search", c_int, [_P, c_int, c_int]),
     ("pfv_enc_session_get_motion_search", c_int, [_P, _P, _P]),

@@ -20,6 +20,7 @@ void launch_enc_pframe_kernels(hipStream_t stream, bool flt, bool small, int com
 #include "pfv_ssim_kernels.hip"
 #include "pfv_deblock_kernels.hip"
 #include "pfv_denoise_kernels.hip"
+#include "pfv_scene_kernels.hip"
 #include "pfv_fullsearch_kernels.hip"
 #include "pfv_hiersearch_kernels.hip"
 #include "pfv_entropy_kernels.hip"
@@ -84,6 +85,7 @@ static const uint8_t H_INV_ZIGZAG[64] = {
 #include "pfv_ssim.hip"
 #include "pfv_deblock.hip"
 #include "pfv_denoise.hip"
+#include "pfv_scene.hip"
 #include "pfv_scale.hip"
 #include "pfv_present.hip"
 #include "pfv_ingest.hip"

@@ -107,7 +107,15 @@ struct pfv_encoder {
     pfv_denoiser *dn = nullptr;            // one stream of width x height; owned; made by the set call
     uint8_t *dn_src = nullptr;             // device: the packed frame that waits for k_denoise; made by the set call
     bool dn_commit = false;                // the entry point that is running commits (encode_*) or does not (probe_*)
-    bool dn_staged = false;                // ... and its filtered frame lies in the staging already: an upload is not repeated
+    bool dn_staged = false;                // ... and its filtered (or measured) frame lies in the staging already: an upload is not repeated
+    // scene-cut detection (pfv_encoder_set_scene_cut): every entry point that stages a frame measures it once, behind the input stages
+    bool sc_on = false;
+    pfv_scene_detector *sc = nullptr;      // one stream of width x height; owned; made by the set call
+    pfv_scene_stats *sc_dev = nullptr;     // device: where k_scene_sum writes; made by the set call
+    PinnedBuf<pfv_scene_stats> sc_host;    // [1]: arrives with the entry point's next synchronisation
+    bool sc_measured = false;              // a frame has been measured since the switch went on
+    uint32_t sc_threshold = PFV_SCENE_THRESHOLD_DEFAULT;
+    int sc_min_interval = 0;
 };
 
 // One step of Decoder::advance_frame's packet loop (src/dec.rs:169-224), found by the header scanner.  FRAME events are
@@ -673,7 +681,7 @@ static int pack_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const 
 {
     if (!planes_given(e, y, u, v)) return fail(e->ctx, PFV_ERR_BAD_ARG, e->rgb_on ? "RGB input is on: y is the picture, u and v must be NULL" : "null plane");
     if (e->finished) return fail(e->ctx, PFV_ERR_STATE, "encoder already finished (src/enc.rs:80)");
-    if ((e->rgb_on || e->scaler || e->dn_on) && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted / resized / filtered planes come back down
+    if ((e->rgb_on || e->scaler || e->dn_on || e->sc_on) && !e->device_entropy) {   // the host entropy path takes its frame from `frame`: the converted / resized / filtered (and measured) planes come back down
         pfv_ctx *ctx = e->ctx;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         int rc = enc_staging(e->hot);
@@ -720,7 +728,7 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
     pfv_enc_session *s = e->hot;
     pfv_ctx *ctx = e->ctx;
     // the filter's state moves once per frame: the entry point's first upload runs it, the frame then lies in the staging for the rest of the call
-    if (e->dn_on && e->dn_staged) return PFV_OK;
+    if ((e->dn_on || e->sc_on) && e->dn_staged) return PFV_OK;
     // what the caller hands over has the size iw x ih; its planar form goes to `planar`: the staging itself, or where it waits for k_scale or
     // k_denoise; `sized`: where the frame of the session's size goes
     const int iw = e->scaler ? e->src_w : e->width, ih = e->scaler ? e->src_h : e->height;
@@ -744,10 +752,18 @@ static int upload_planes(pfv_encoder *e, const uint8_t *y, const uint8_t *u, con
         const int rc = scale_launch(e->scaler, 1, e->scale_src, PFV_FRAME_PACKED, ny + 2 * nc, sized, fb);
         if (rc) return rc;
     }
-    if (!e->dn_on) return PFV_OK;
-    const int rc = denoise_launch(e->dn, 0, 1, e->dn_src, PFV_FRAME_PACKED, fb, s->st_frames, fb, e->dn_commit ? 1 : 0, "pfv_encoder");   // one k_denoise into the staging
-    if (!rc) e->dn_staged = true;
-    return rc;
+    if (e->dn_on) {   // one k_denoise into the staging
+        const int rc = denoise_launch(e->dn, 0, 1, e->dn_src, PFV_FRAME_PACKED, fb, s->st_frames, fb, e->dn_commit ? 1 : 0, "pfv_encoder");
+        if (rc) return rc;
+    }
+    if (e->sc_on) {   // the staged frame measured against the detector's state: one launch group, the 40 bytes on their way down
+        const int rc = scene_launch(e->sc, 0, 1, 0, s->st_frames, PFV_FRAME_PACKED, 0, e->dn_commit ? 1 : 0, e->sc_dev, "pfv_encoder");
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(e->sc_host.data(), e->sc_dev, sizeof(pfv_scene_stats), hipMemcpyDeviceToHost, ctx->stream));
+        e->sc_measured = true;
+    }
+    if (e->dn_on || e->sc_on) e->dn_staged = true;
+    return PFV_OK;
 }
 
 // One frame through the device entropy stage: planes up (unless the i-frame budget's probe has put them there: `staged`), kernels, payload size
@@ -866,6 +882,43 @@ PFV_API int pfv_encoder_set_denoise(pfv_encoder *e, int on, const uint8_t spatia
     if ((rc = pfv_denoiser_set_strength(e->dn, spatial, temporal))) return rc;
     e->dn_on = true;
     return enc_input_scratch(e);
+}
+
+// Scene-cut detection: while on, upload_planes measures the staged frame once per entry point (the encode_* calls commit the detector's state,
+// the probe_* calls do not) and pfv_encoder_encode_frame takes rule 1b from the score.
+PFV_API int pfv_encoder_set_scene_cut(pfv_encoder *e, int on, uint32_t threshold_q8, int radius, int min_interval)
+{
+    if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
+    if (!on) {
+        e->sc_on = false;
+        return PFV_OK;
+    }
+    pfv_ctx *ctx = e->ctx;
+    if (radius < 0 || radius > kSceneMaxR || min_interval < 0) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_encoder_set_scene_cut: the radius is 0 .. 7, min_interval not negative");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = enc_staging(e->hot);
+    if (rc) return rc;
+    if (!e->sc && !(e->sc = pfv_scene_detector_create(ctx, e->width, e->height, 1, 0, &rc))) return rc;
+    if (!e->sc_dev) HIP_TRY(ctx, hipMalloc((void **)&e->sc_dev, sizeof(pfv_scene_stats)));
+    if (!e->sc_host.resize(1)) return fail(ctx, PFV_ERR_NOMEM, "pinned staging for the scene stats");
+    if (!e->sc_on) {   // switched on: the detector starts without a past
+        if ((rc = pfv_scene_detector_reset(e->sc, 0, 1))) return rc;
+        e->sc_measured = false;
+    }
+    if ((rc = pfv_scene_detector_set_radius(e->sc, radius))) return rc;
+    e->sc_threshold = threshold_q8;
+    e->sc_min_interval = min_interval;
+    e->sc_on = true;
+    return PFV_OK;
+}
+PFV_API int pfv_encoder_last_scene(pfv_encoder *e, pfv_scene_stats *out)
+{
+    if (!e || !out) return fail(e ? e->ctx : nullptr, PFV_ERR_BAD_ARG, "pfv_encoder_last_scene: bad argument");
+    if (!e->sc_on || !e->sc_measured) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_last_scene: scene-cut detection is off or has measured no frame yet");
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    HIP_TRY(e->ctx, hipStreamSynchronize(e->ctx->stream));   // an entry point that failed may have left the download in flight
+    *out = *e->sc_host.data();
+    return PFV_OK;
 }
 
 // Frame reports: with them on, every encode_* call also measures the frame it was given against the reconstruction it leaves in prev_frame
@@ -1233,7 +1286,8 @@ static bool rd_prefers_iframe(const pfv_encoder *e, uint32_t pbytes, const uint6
 PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, int *type_out)
 {
     if (!e) return fail(nullptr, PFV_ERR_BAD_ARG, "null encoder");
-    if (!enc_fourstep(e->hot)) return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_encode_frame: the frame type comes from the p-frame probes, which follow the four-step search only");
+    if (!e->sc_on && !enc_fourstep(e->hot))
+        return fail(e->ctx, PFV_ERR_STATE, "pfv_encoder_encode_frame: the frame type comes from the p-frame probes, which follow the four-step search only (or from pfv_encoder_set_scene_cut)");
     if (e->report_on) e->report_state = -1;   // until this call has written its packet
     if (e->ssim_on) e->ssim_state = -1;
     e->dn_commit = true; e->dn_staged = false;   // the frame this call uploads moves the filter's state
@@ -1241,8 +1295,25 @@ PFV_API int pfv_encoder_encode_frame(pfv_encoder *e, const uint8_t *y, const uin
     if (rc) return rc;
     pfv_enc_session *s = e->hot;
     int type = 1;
+    bool cut = false;
+    if (e->sc_on) {   // the frame up and measured before anything is decided (the host entropy path did both in pack_frame)
+        pfv_ctx *ctx = e->ctx;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (e->device_entropy) {
+            rc = enc_staging(s);
+            if (!rc) rc = upload_planes(e, y, u, v);
+            if (rc) return rc;
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        cut = pfv_scene_score_q8(e->sc_host.data()) >= e->sc_threshold && e->since_iframe + 1 >= std::max(1, e->sc_min_interval);   // d of pfv_scene_plan: this frame counted
+    }
     if (e->n_written == 0 || e->poisoned || (e->gop_max > 0 && e->since_iframe >= e->gop_max)) {   // 1: a forced i-frame
         rc = write_iframe(e, y, u, v);
+    } else if (cut) {                                                                               // 1b: a scene cut: an i-frame, no p-frame sizing
+        rc = write_iframe(e, y, u, v);
+    } else if (!enc_fourstep(s)) {                                                                  // PFV_SEARCH_FULL / _HIER under scene-cut detection: a p-frame at the current rung
+        type = 2;
+        rc = write_pframe(e, y, u, v, true);
     } else {
         uint32_t psize[kMaxRungs], isize[kMaxRungs], counts[kMaxRungs][kPProbeStats];
         uint64_t psse[kMaxRungs][3], isse[kMaxRungs][3];
@@ -1324,7 +1395,7 @@ PFV_API int pfv_encoder_drain(pfv_encoder *e, const uint8_t **data, size_t *len)
 PFV_API void pfv_encoder_destroy(pfv_encoder *e)
 {
     if (!e) return;
-    if (e->rgb_scratch || e->scaler || e->dn) {
+    if (e->rgb_scratch || e->scaler || e->dn || e->sc) {
         (void)hipSetDevice(e->ctx->device);
         (void)hipStreamSynchronize(e->ctx->stream);
         if (e->rgb_scratch) (void)hipFree(e->rgb_scratch);
@@ -1332,6 +1403,8 @@ PFV_API void pfv_encoder_destroy(pfv_encoder *e)
         if (e->dn_src) (void)hipFree(e->dn_src);
         pfv_scaler_destroy(e->scaler);
         pfv_denoiser_destroy(e->dn);
+        pfv_scene_detector_destroy(e->sc);
+        if (e->sc_dev) (void)hipFree(e->sc_dev);
     }
     pfv_enc_session_destroy(e->hot);
     delete e;

@@ -86,9 +86,28 @@ class Encoder:
         s, t = strengths(spatial), strengths(temporal)
         self.ctx.check(self.ctx._lib.pfv_encoder_set_denoise(self.handle, 1 if on else 0, ptr(s), ptr(t)))
 
+    def set_scene_cut(self, on=True, threshold_q8: int | None = None, radius: int | None = None, min_interval: int = 0):
+        """scene-cut detection on the staged frame of every encode_* (committed) and probe_* (uncommitted) call; encode_frame then writes an
+        i-frame where the score reaches threshold_q8 and min_interval frames have followed the last i-frame, and works in "full" / "hier"
+        search mode too (pfv_encoder_set_scene_cut)"""
+        from .scene import RADIUS_DEFAULT, THRESHOLD_DEFAULT
+        self.ctx.check(self.ctx._lib.pfv_encoder_set_scene_cut(self.handle, 1 if on else 0, int(THRESHOLD_DEFAULT if threshold_q8 is None else threshold_q8),
+                                                               int(RADIUS_DEFAULT if radius is None else radius), int(min_interval)))
+
+    @property
+    def last_scene(self):
+        """SceneStats of the last call that measured a frame (pfv_encoder_last_scene); PfvError(PFV_ERR_STATE) when the switch is off or no
+        frame has been measured"""
+        import numpy as np
+        from .scene import STATS_DTYPE, SceneStats
+        r = np.zeros(1, dtype=STATS_DTYPE)
+        self.ctx.check(self.ctx._lib.pfv_encoder_last_scene(self.handle, ptr(r)))
+        return SceneStats.from_record(r[0])
+
     def set_motion_search(self, mode="fourstep", radius: int = 0):
         """the motion search of the p-frames that follow: "fourstep", "full" with a radius of 1..15 or "hier" with an even radius of 2..62
-        (pfv_encoder_set_motion_search); full and hier mode exclude the p-frame probe, the p-frame floors and encode_frame"""
+        (pfv_encoder_set_motion_search); full and hier mode exclude the p-frame probe, the p-frame floors and -- without set_scene_cut --
+        encode_frame"""
         from ._lib import search_mode
         self.ctx.check(self.ctx._lib.pfv_encoder_set_motion_search(self.handle, search_mode(mode), int(radius)))
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate / distortion of the codec over its quality setting, measured on the device.
 
-    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise] [--search full[,R]|hier,R] [--pan DX,DY] [--time-search]
+    python tools/rd_curve.py WIDTH HEIGHT FRAMES [--gop G] [--kind pan|low_motion|static] [--qualities 0,2,5,10] [--time-kernel] [--probe] [--probe-p] [--probe-rd] [--probe-p-rd] [--ssim] [--time-ssim] [--deblock] [--dump DIR] [--time-deblock] [--time-present] [--time-ingest] [--time-scale] [--denoise SS,ST] [--time-denoise] [--search full[,R]|hier,R] [--pan DX,DY] [--time-search] [--scene-cut [THRESHOLD,R]] [--time-scene]
 
 Per quality the synthetic clip goes through ``Encoder`` with frame reports on (pfv_encoder_set_frame_report: the k_sse_* kernels
 compare every frame with the reconstruction the encoder leaves behind); one JSON line per quality: bytes per frame, split into
@@ -31,6 +31,18 @@ skipped (noisy_skipped_share, dn_skipped_share).  --dump DIR also writes q<quali
 --time-denoise (on the GPU box) adds one more line: k_denoise (committed, steady state, strengths 6 / 6, packed and padded source) beside
 k_deblock and k_crop_frames on the same 96 x 1080p frames -- HIP events on the context's stream around every launch, warm-up, the median of
 the samples, alternating in three rounds.  With PFV_HIP_LIB set only one WIDTH x HEIGHT stream runs: the row is printed, its times mean nothing.
+
+--scene-cut [THRESHOLD,R] (default 176,5) adds, per quality, one line {"scene_cut": ...}: a clip spliced in segments from
+SyntheticStream(SEED, "pan") and SyntheticStream(SEED + 17, "low_motion") (WIDTH x HEIGHT, FRAMES frames; "splices" names the frames) is measured by
+pfv_frames_scene at radius R ("scores_q8") and encoded twice through pfv_encoder with explicit types: an i-frame every 15 frames (fixed_*) and the
+types pfv_scene_plan makes of the stats at THRESHOLD, min_interval 1, max_interval 15 (planned_*): bytes, i-frames, worst and mean PSNR-YUV of the
+frame reports.
+
+--time-scene (on the GPU box) adds one more line: the three scene kernels on 96 x 1080p frames in HBM (pfv_scene_detector_run_dev, uncommitted,
+steady state, R = 4 and R = 7) and on one 4K x 60-frame clip (pfv_scene_detector_run_clip_dev, R = 4) -- per kernel from the events
+pfv_scene_detector_run_timed_dev records between them, per launch group from an event pair -- beside the k_sse_mb + k_sse_sum pair on the same two
+frames and the default p-frame encode; warm-up, the median of the samples, alternating in three rounds.  With PFV_HIP_LIB set two WIDTH x HEIGHT
+streams and a three-frame clip run: the row is printed, its times mean nothing.
 
 --search full[,R] (R = 1 .. 15, default 15) adds, per quality, the clip encoded with both motion searches (pfv_encoder_set_motion_search) side by
 side: four_ / full_ stream_bytes, psnr_yuv (mean over the frames, frame reports), and the coded and skipped p-frame macroblocks (an encoder
@@ -419,6 +431,116 @@ def time_denoise(pkg, ctx, n_streams=96, w=1920, h=1080, warmup=5, samples=30, r
     moved = {"denoise_packed": n_streams * 4 * fb, "denoise_padded": n_streams * (pfb + 3 * fb), "deblock": n_streams * (pfb + fb), "crop": n_streams * (pfb + fb)}
     return {"shape": f"{n_streams} x {w}x{h}", "samples_per_round": samples, "rounds": rounds, **{f"{k}_ms": v for k, v in med.items()},
             **{f"{k}_GBps": moved[k] / med[k] / 1e6 if med[k] else None for k in med}, "rounds_ms": res}
+
+
+def scene_cut_line(pkg, ctx, w, h, n_frames, quality, threshold, radius, max_interval=15):
+    """a clip spliced from SyntheticStream(SEED, "pan") and SyntheticStream(SEED + 17, "low_motion") in segments, encoded twice through
+    pfv_encoder with explicit frame types: an i-frame every `max_interval` frames, and the types pfv_scene_plan makes of the detector's stats
+    (min_interval 1, the same max_interval).  Bytes and worst-frame PSNR-YUV from the frame reports."""
+    from pretty_fast_video_amd.synth import SEED
+    segment = 11 if n_frames >= 22 else max(3, n_frames // 3)
+    a, b = pkg.SyntheticStream(w, h, seed=SEED, kind="pan"), pkg.SyntheticStream(w, h, seed=SEED + 17, kind="low_motion")
+    clip = np.stack([(b if (t // segment) % 2 else a).frame(t) for t in range(n_frames)])
+    stats = pkg.frames_scene(ctx, w, h, clip, radius).reshape(-1)
+    scores = [pkg.scene_score(s) for s in stats]
+    planned = pkg.scene_plan(stats, threshold, 1, max_interval).tolist()
+    fixed = [1 if t % max_interval == 0 else 2 for t in range(n_frames)]
+    line = {"threshold_q8": threshold, "radius": radius, "quality": quality, "width": w, "height": h, "frames": n_frames, "segment": segment,
+            "splices": [t for t in range(1, n_frames) if t % segment == 0], "scores_q8": scores, "planned_types": planned, "fixed_types": fixed}
+    for name, types in (("planned", planned), ("fixed", fixed)):
+        enc = pkg.Encoder(io.BytesIO(), w, h, 30, quality, ctx, frame_report=True)
+        reports = []
+        for ty, f in zip(types, clip):
+            (enc.encode_iframe if ty == 1 else enc.encode_pframe)(pkg.VideoFrame.from_packed(w, h, f))
+            reports.append(enc.last_report)
+        enc.finish()
+        enc.close()
+        line.update({f"{name}_bytes": sum(r.packet_bytes for r in reports), f"{name}_iframes": types.count(1),
+                     f"{name}_worst_psnr": min(r.psnr_yuv for r in reports), f"{name}_mean_psnr": float(sum(r.psnr_yuv for r in reports) / len(reports))})
+    return line
+
+
+def time_scene(pkg, ctx, n_streams=96, w=1920, h=1080, clip=(3840, 2160, 60), quality=5, warmup=5, samples=30, rounds=3):
+    """the three scene kernels at n_streams x w x h (run_dev, uncommitted, R = 4 and R = 7) and on one clip (run_clip_dev, R = 4): per kernel from
+    the events pfv_scene_detector_run_timed_dev records between them, per launch group from an event pair around run_dev / run_clip_dev; beside
+    them k_sse_mb + k_sse_sum on the same two frames and the default p-frame encode.  Medians, the cases alternating in every round."""
+    lib = ctx._lib
+    P = ctypes.c_void_p
+    fb, tb = int(lib.pfv_frame_bytes(w, h)), int(lib.pfv_total_blocks(w, h))
+    f0, f1 = ctx.alloc(fb * n_streams), ctx.alloc(fb * n_streams)
+    coef, mv, has = ctx.alloc(n_streams * tb * 512), ctx.alloc(n_streams * tb * 2), ctx.alloc(n_streams * tb)
+    cw, ch, cn = clip
+    cfb = int(lib.pfv_frame_bytes(cw, ch))
+    frames = ctx.alloc(cfb * cn)
+    stats, sse = ctx.alloc(40 * max(n_streams, cn)), ctx.alloc(8 * 3 * n_streams)
+    seeds = np.arange(1, n_streams + 1, dtype=np.uint64)
+    ctx.synth_frames_dev(w, h, seeds, 0, f0)
+    ctx.synth_frames_dev(w, h, seeds, 1, f1)
+    for t in range(cn):
+        ctx.synth_frames_dev(cw, ch, seeds[:1], t, frames + t * cfb)
+    enc = pkg.EncoderSession(ctx, w, h, quality, n_streams)
+    det = pkg.SceneDetector(ctx, w, h, n_streams)
+    cdet = pkg.SceneDetector(ctx, cw, ch, 1, max_clip_frames=cn)
+    det.run_dev(f0, stats)                                     # primes: the timed runs are the steady state
+    cdet.run_clip_dev(frames, 1, stats)
+    ctx.check(lib.pfv_frames_sse_dev(ctx.handle, w, h, n_streams, P(f0), 0, 0, P(f1), 0, 0, P(sse), None))      # makes the map scratch
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+
+    def median_ms(fn, before=None):
+        got = []
+        for k in range(warmup + samples):
+            if before:
+                before()
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ms = ctypes.c_float()
+            ctx.check(lib.pfv_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
+            if k >= warmup:
+                got.append(float(ms.value))
+        return statistics.median(got)
+
+    def kernels_ms(d, src, n, radius, is_clip):
+        d.set_radius(radius)
+        got = [d.run_timed_dev(src, n, stats, clip=is_clip) for _ in range(warmup + samples)][warmup:]
+        return [statistics.median(g_[i] for g_ in got) for i in range(3)]
+
+    def group(d, radius, fn):
+        d.set_radius(radius)
+        return median_ms(fn)
+    cases = {
+        "run_dev_r4": lambda: group(det, 4, lambda: det.run_dev(f1, stats, commit=False)),
+        "run_dev_r7": lambda: group(det, 7, lambda: det.run_dev(f1, stats, commit=False)),
+        "run_clip_dev_r4": lambda: group(cdet, 4, lambda: cdet.run_clip_dev(frames, cn, stats, commit=False)),
+        "sse_pair": lambda: median_ms(lambda: ctx.check(lib.pfv_frames_sse_dev(ctx.handle, w, h, n_streams, P(f0), 0, 0, P(f1), 0, 0, P(sse), None))),
+        "enc_pframe": lambda: median_ms(lambda: enc.encode_pframe_dev(f1, mv, has, coef), before=lambda: enc.encode_iframe_dev(f0, coef)),
+    }
+    res = {k: [] for k in cases}
+    stages = {"r4": [], "r7": [], "clip_r4": []}
+    for _ in range(rounds):                       # alternate, so that whatever else the box is doing meets all of them
+        for key, fn in cases.items():
+            res[key].append(fn())
+        stages["r4"].append(kernels_ms(det, f1, n_streams, 4, False))
+        stages["r7"].append(kernels_ms(det, f1, n_streams, 7, False))
+        stages["clip_r4"].append(kernels_ms(cdet, frames, cn, 4, True))
+    ctx.sync()
+    ctx.event_destroy(e0); ctx.event_destroy(e1)
+    det.close(); cdet.close(); enc.close()
+    for p in (f0, f1, coef, mv, has, frames, stats, sse):
+        ctx.free(p)
+    med = {k: statistics.median(v) for k, v in res.items()}
+    st = {k: [statistics.median(x[i] for x in v) for i in range(3)] for k, v in stages.items()}
+    over = lambda x, y: x / y if y else None      # noqa: E731  (an emulated device has no clock: its events are 0 ms apart)
+    blocks = n_streams * ((w >> 2) >> 3) * ((h >> 2) >> 3)
+    return {"shape": f"{n_streams} x {w}x{h}", "clip": f"{cn} x {cw}x{ch}", "samples_per_round": samples, "rounds": rounds,
+            "quarter_ms": st["r4"][0], "cost_r4_ms": st["r4"][1], "cost_r7_ms": st["r7"][1], "sum_ms": st["r4"][2],
+            "clip_quarter_ms": st["clip_r4"][0], "clip_cost_r4_ms": st["clip_r4"][1], "clip_sum_ms": st["clip_r4"][2],
+            **{f"{k}_ms": v for k, v in med.items()},
+            "quarter_GBps": over(n_streams * (w * h + (w >> 2) * (h >> 2)) / 1e6, st["r4"][0]),
+            "cost_r4_ns_per_block": over(st["r4"][1] * 1e6, blocks), "cost_r7_ns_per_block": over(st["r7"][1] * 1e6, blocks),
+            "run_dev_r4_over_enc_pframe": over(med["run_dev_r4"], med["enc_pframe"]), "run_dev_r4_over_sse_pair": over(med["run_dev_r4"], med["sse_pair"]),
+            "blocks": blocks, "rounds_ms": res}
 
 
 def pan_clip(w, h, n_frames, dx, dy, seed=7):
@@ -1349,6 +1471,8 @@ def main():
     ap.add_argument("--search", default=None, metavar="full[,R]|hier,R")
     ap.add_argument("--pan", default=None, metavar="DX,DY")
     ap.add_argument("--time-search", action="store_true")
+    ap.add_argument("--scene-cut", nargs="?", const="176,5", default=None, metavar="THRESHOLD,R")
+    ap.add_argument("--time-scene", action="store_true")
     a = ap.parse_args()
     assert a.frames >= 1 and a.gop >= 1
     pkg = load()
@@ -1370,6 +1494,14 @@ def main():
             emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the row only
             kw = dict(n_streams=2, w=a.width, h=a.height, warmup=1, samples=2, rounds=1) if emu else {}
             print(json.dumps({"time_search": time_search(pkg, ctx, **kw)}), flush=True)
+        if a.scene_cut:
+            thr, rad = (int(x) for x in a.scene_cut.split(","))
+            for q in [int(x) for x in a.qualities.split(",") if x != ""]:
+                print(json.dumps({"scene_cut": scene_cut_line(pkg, ctx, a.width, a.height, a.frames, q, thr, rad)}), flush=True)
+        if a.time_scene:
+            emu = bool(os.environ.get("PFV_HIP_LIB"))      # another build of the C ABI (the CPU emulator): nothing to time, the row only
+            kw = dict(n_streams=2, w=a.width, h=a.height, clip=(a.width, a.height, 3), warmup=1, samples=2, rounds=1) if emu else {}
+            print(json.dumps({"time_scene": time_scene(pkg, ctx, **kw)}), flush=True)
         if a.time_ssim:
             print(json.dumps({"time_ssim": time_ssim(pkg, ctx)}), flush=True)
         if a.time_deblock:
