@@ -40,6 +40,12 @@ PFV_API void *pfv_ctx_stream(pfv_ctx *ctx);
  *                                          below 2^24 for the session's tables, checked at session creation; always true for
  *                                          quality 0..10 -- and in i32 otherwise
  *       PFV_ENC_TRANSFORM_INT             always the i32 kernels
+ *   PFV_OPT_DEC_TRANSFORM  how the decode kernels evaluate the inverse transform (src/dct.rs:241-293):
+ *       PFV_DEC_TRANSFORM_AUTO (default)  in f32 for every wavefront and pass whose dequantised values v = coefficient x table entry --
+ *                                          formed in i32 as ever, wrapped where the reference wraps -- all satisfy |v| <= pfv_dec_float_guard(),
+ *                                          the bound below which f32 reproduces the integer butterflies bit for bit; in i32 for the others.
+ *                                          Decided on the device from the data: any coefficients, any tables
+ *       PFV_DEC_TRANSFORM_INT             always the i32 kernels
  *   PFV_OPT_TILE_COMPACTION  1 (default): the p-frame encoder transforms only CODED macroblocks where that saves work -- a
  *       skipped macroblock is not transformed by the reference either (src/common.rs:221-222) -- by moving the coded macroblocks of
  *       a 128 x 64 tile together before the transform phase; 0: every wavefront transforms its own strip (measurements);
@@ -65,11 +71,12 @@ PFV_API void *pfv_ctx_stream(pfv_ctx *ctx);
  *       read (1..1024, default 96; a round in which no lane has a new start ends them) */
 typedef enum pfv_option {
     PFV_OPT_ENC_TRANSFORM = 1, PFV_OPT_TILE_COMPACTION = 2, PFV_OPT_LANE_MAPPING = 3, PFV_OPT_ENTROPY_DECODE = 4,
-    PFV_OPT_ENTDEC_LANE_BITS = 5, PFV_OPT_ENTDEC_LAUNCHES = 6, PFV_OPT_ENTDEC_INNER_ROUNDS = 7
+    PFV_OPT_ENTDEC_LANE_BITS = 5, PFV_OPT_ENTDEC_LAUNCHES = 6, PFV_OPT_ENTDEC_INNER_ROUNDS = 7, PFV_OPT_DEC_TRANSFORM = 8
 } pfv_option;
 enum { PFV_ENTROPY_DECODE_AUTO = 0, PFV_ENTROPY_DECODE_HOST = 1, PFV_ENTROPY_DECODE_DEVICE = 2 };
 enum { PFV_LANES_AUTO = 0, PFV_LANES_PER_MB_8 = 1, PFV_LANES_PER_MB_16 = 2 };
 enum { PFV_ENC_TRANSFORM_AUTO = 0, PFV_ENC_TRANSFORM_INT = 1 };
+enum { PFV_DEC_TRANSFORM_AUTO = 0, PFV_DEC_TRANSFORM_INT = 1 };
 PFV_API int pfv_ctx_set_option(pfv_ctx *ctx, int option, int value);
 PFV_API int pfv_ctx_get_option(pfv_ctx *ctx, int option, int *value);
 
@@ -264,6 +271,14 @@ PFV_API int pfv_dec_set_output_dev(pfv_dec_session *s, uint8_t *frames_out_dev);
  * frames_out_dev = first frame + t * pfv_frame_bytes the decoded stream appears in display order. */
 PFV_API int pfv_dec_set_output_strided_dev(pfv_dec_session *s, uint8_t *frames_out_dev, size_t stride_bytes);
 PFV_API int pfv_dec_session_set_window(pfv_dec_session *s, int first, int count);
+/* [C] The bound of PFV_DEC_TRANSFORM_AUTO, and which road a session's launches took (tests, measurements).  A wavefront is one launch's
+ * unit of work that owns a macroblock: a strip of 8 macroblocks, or 4 under the 16-lane mapping.  enable_path_stats(on = 1) starts
+ * counting from zero (again), 0 stops; path_stats waits for the stream and reports, since then, the wavefronts that ran a pass of the
+ * inverse transform in i32 because the guard failed, and all wavefronts launched (p-frame wavefronts without a coded macroblock included:
+ * they transform nothing).  A session that does not count hands its kernels a null counter. */
+PFV_API int pfv_dec_float_guard(void);
+PFV_API int pfv_dec_session_enable_path_stats(pfv_dec_session *s, int on);
+PFV_API int pfv_dec_session_path_stats(pfv_dec_session *s, int64_t *int_waves, int64_t *total_waves);
 /* 1 (default): packet payloads come from the device entropy stage; 0: from the host serialisers.  Same bytes. */
 PFV_API int pfv_encoder_set_device_entropy(pfv_encoder *e, int on);
 /* ------------------------------------------------------------------ distortion on the device  [B]

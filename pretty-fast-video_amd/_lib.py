@@ -35,6 +35,8 @@ PFV_OPT_ENTROPY_DECODE = 4
 PFV_OPT_ENTDEC_LANE_BITS, PFV_OPT_ENTDEC_LAUNCHES, PFV_OPT_ENTDEC_INNER_ROUNDS = 5, 6, 7
 PFV_ENTROPY_DECODE_AUTO, PFV_ENTROPY_DECODE_HOST, PFV_ENTROPY_DECODE_DEVICE = 0, 1, 2
 PFV_ENC_TRANSFORM_AUTO, PFV_ENC_TRANSFORM_INT = 0, 1
+PFV_OPT_DEC_TRANSFORM = 8
+PFV_DEC_TRANSFORM_AUTO, PFV_DEC_TRANSFORM_INT = 0, 1
 PFV_FRAME_PACKED, PFV_FRAME_PADDED = 0, 1              # operand layouts of pfv_frames_sse_dev
 PFV_DEBLOCK_OFF, PFV_DEBLOCK_AUTO, PFV_DEBLOCK_FIXED = 0, 1, 2   # pfv_dec_set_deblock / pfv_decoder_set_deblock
 PFV_PIX_RGB8, PFV_PIX_RGBA8, PFV_PIX_BGRA8 = 0, 1, 2             # pixel formats of pfv_frames_to_rgb* and the decoders' RGB outputs
@@ -151,6 +153,9 @@ SIGNATURES = [
     ("pfv_dec_set_output_dev", c_int, [_P, _P]),
     ("pfv_dec_set_output_strided_dev", c_int, [_P, _P, c_size_t]),
     ("pfv_dec_session_set_window", c_int, [_P, c_int, c_int]),
+    ("pfv_dec_float_guard", c_int, []),
+    ("pfv_dec_session_enable_path_stats", c_int, [_P, c_int]),
+    ("pfv_dec_session_path_stats", c_int, [_P, POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
     ("pfv_dec_get_frame", c_int, [_P, _P]),
     ("pfv_dec_framebuffer", c_int, [_P, _P]),
     ("pfv_dec_check", c_int, [_P]),

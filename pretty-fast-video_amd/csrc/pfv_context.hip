@@ -1,6 +1,9 @@
 // pfv_context.hip -- context: pfv_ctx, options, timing events, HIP graphs (pfv_ctx_*, pfv_event_*, pfv_graph_*).
 // Part of the one translation unit of the C ABI: included by pfv_capi.hip, in this order, never compiled on its own.
 // ------------------------------------------------------------------ context
+#ifndef PFV_DEC_TRANSFORM_DEFAULT   // A/B builds (tools/gpu_ab.sh): -DPFV_DEC_TRANSFORM_DEFAULT=PFV_DEC_TRANSFORM_INT times the integer decoders under bench.py
+#define PFV_DEC_TRANSFORM_DEFAULT PFV_DEC_TRANSFORM_AUTO
+#endif
 constexpr int kCtxScratch = 9;   // slots 0..5, 7: plane operators and host-pointer forms; 6: pfv_quality.hip's map; 8: pfv_ssim.hip's map
 struct pfv_ctx {
     int device = 0;
@@ -15,6 +18,7 @@ struct pfv_ctx {
     int n_cus = 256;             // compute units of the device (persistent-kernel grid sizing)
     bool capturing = false;      // a pfv_graph_begin is open on the stream
     int opt_enc_transform = PFV_ENC_TRANSFORM_AUTO;   // pfv_ctx_set_option(PFV_OPT_ENC_TRANSFORM)
+    int opt_dec_transform = PFV_DEC_TRANSFORM_DEFAULT; // pfv_ctx_set_option(PFV_OPT_DEC_TRANSFORM)
     int opt_tile_compaction = 1;                      // pfv_ctx_set_option(PFV_OPT_TILE_COMPACTION)
     int opt_lane_mapping = PFV_LANES_AUTO;            // pfv_ctx_set_option(PFV_OPT_LANE_MAPPING)
     int opt_entropy_decode = PFV_ENTROPY_DECODE_AUTO; // pfv_ctx_set_option(PFV_OPT_ENTROPY_DECODE)
@@ -69,6 +73,7 @@ extern "C" {
 #endif
 PFV_API const char *pfv_version(void) { return "pfv-hip 0.2 (gfx950; pfv-rs 0.2.2 / codec 2.1.1 hot path; src " PFV_BUILD_ID ")"; }
 PFV_API int pfv_pad16(int x) { return pad16(x); }
+PFV_API int pfv_dec_float_guard(void) { return kDecFloatGuard; }
 
 PFV_API const char *pfv_last_error(pfv_ctx *ctx) { return ctx ? ctx->err.c_str() : g_tls_err.c_str(); }
 
@@ -79,6 +84,10 @@ PFV_API int pfv_ctx_set_option(pfv_ctx *ctx, int option, int value)
     case PFV_OPT_ENC_TRANSFORM:
         if (value != PFV_ENC_TRANSFORM_AUTO && value != PFV_ENC_TRANSFORM_INT) return fail(ctx, PFV_ERR_BAD_ARG, "PFV_OPT_ENC_TRANSFORM: unknown value");
         ctx->opt_enc_transform = value;
+        return PFV_OK;
+    case PFV_OPT_DEC_TRANSFORM:
+        if (value != PFV_DEC_TRANSFORM_AUTO && value != PFV_DEC_TRANSFORM_INT) return fail(ctx, PFV_ERR_BAD_ARG, "PFV_OPT_DEC_TRANSFORM: unknown value");
+        ctx->opt_dec_transform = value;
         return PFV_OK;
     case PFV_OPT_TILE_COMPACTION:
         if (value < 0 || value > 2) return fail(ctx, PFV_ERR_BAD_ARG, "PFV_OPT_TILE_COMPACTION: 0, 1 or 2");
@@ -113,6 +122,7 @@ PFV_API int pfv_ctx_get_option(pfv_ctx *ctx, int option, int *value)
     if (!ctx || !value) return fail(ctx, PFV_ERR_BAD_ARG, "pfv_ctx_get_option: bad argument");
     switch (option) {
     case PFV_OPT_ENC_TRANSFORM: *value = ctx->opt_enc_transform; return PFV_OK;
+    case PFV_OPT_DEC_TRANSFORM: *value = ctx->opt_dec_transform; return PFV_OK;
     case PFV_OPT_TILE_COMPACTION: *value = ctx->opt_tile_compaction; return PFV_OK;
     case PFV_OPT_LANE_MAPPING: *value = ctx->opt_lane_mapping; return PFV_OK;
     case PFV_OPT_ENTROPY_DECODE: *value = ctx->opt_entropy_decode; return PFV_OK;

@@ -550,15 +550,19 @@ __device__ __forceinline__ void forward_half(int (&v)[2][8], int *xw, int m, int
 // upper one is not (t = 127 gives prev + 254, t = 128 would give 255 for prev = 0), so it is kept.
 // |t| < 2^23, so 2t cannot overflow.
 // reference src/dct.rs:75-86 (decode) + src/common.rs:314-316 (columns first, then rows).
-__device__ __forceinline__ void inverse_half(int (&v)[2][8], int *xw, int m, int i, const LaneQ &lq)
+// The two steps are callable on their own: the decoders look at the dequantised values between them (dec_float_guard).
+__device__ __forceinline__ void dequant_half(int (&v)[2][8], const LaneQ &lq)
 {
-    int *mb = xw + m * kMBPitch;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int deq = lq.deq(k);
         v[0][k] = wmul24(v[0][k], deq);
         v[1][k] = wmul24(v[1][k], deq);
     }
+}
+__device__ __forceinline__ void inverse_transform_half(int (&v)[2][8], int *xw, int m, int i)
+{
+    int *mb = xw + m * kMBPitch;
     idct8(v[0]);   // dct_inverse_transform_columns
     idct8(v[1]);
     cols_to_rows2(v, mb, i, m & 3);
@@ -568,6 +572,11 @@ __device__ __forceinline__ void inverse_half(int (&v)[2][8], int *xw, int m, int
 #pragma unroll
         for (int k = 0; k < 8; k++) v[s][k] = min(v[s][k] >> 8, 127);
     }
+}
+__device__ __forceinline__ void inverse_half(int (&v)[2][8], int *xw, int m, int i, const LaneQ &lq)
+{
+    dequant_half(v, lq);
+    inverse_transform_half(v, xw, m, i);
 }
 // gather the lane's column of quantised coefficients out of the zigzag-ordered stage
 __device__ __forceinline__ void gather_half(int (&v)[2][8], const int *xw, int m, const LaneQ &lq)
@@ -593,8 +602,8 @@ __device__ __forceinline__ void gather_half(int (&v)[2][8], const int *xw, int m
 // mixed stream costs ~4.2 cycles: (1) v_pk_add/mul/fma_f32 work on two values (the lane's two subblocks) per
 // instruction, (2) fma fuses the shift-and-add pairs of the integer butterfly (30 packed instructions for two 8-point
 // forward transforms instead of 2 x 48), and truncation toward zero is one v_trunc_f32 instead of a sign-bias sequence
-// (72 instead of 2 x 70 for two inverse transforms).  The decoders keep the integer form: they must wrap exactly like i32
-// on hostile coefficients.
+// (72 instead of 2 x 70 for two inverse transforms).  The decoders must wrap exactly like i32 on hostile coefficients: they run
+// fidct8 only behind a per-wavefront check of the dequantised values and keep the integer form beside it (dec_float_guard).
 typedef float f2 __attribute__((vector_size(8)));   // lane's two subblocks, element s = subblock s
 __device__ __forceinline__ f2 f2s(float x) { return f2{x, x}; }
 __device__ __forceinline__ f2 f2trunc(f2 x) { return f2{__builtin_truncf(x[0]), __builtin_truncf(x[1])}; }
@@ -761,17 +770,23 @@ __device__ __forceinline__ void forward_half_f(f2 (&x)[8], int *xw, int m, int i
 //           instruction's rounding rule on its own).
 constexpr float kPixelBias = 127.501953125f;   // 128 - 1/2 + 1/512
 __device__ __forceinline__ f2 iframe_pixel_f(f2 x) { return x * f2s(1.0f / 256.0f) + f2s(kPixelBias); }   // one v_pk_fma_f32; exact wherever the result matters (|x / 256| < 2^15)
+// inverse_transform_half_f: the same from DEQUANTISED values (the decoders' float path, which dequantises in integers: dec_float_guard)
 template <bool PIXEL>
-__device__ __forceinline__ void inverse_half_f(f2 (&c)[8], int *xw, int m, int i, const LaneQ &lq)
+__device__ __forceinline__ void inverse_transform_half_f(f2 (&c)[8], int *xw, int m, int i)
 {
     int *mb = xw + m * kMBPitch;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c[k] = c[k] * f2s(lq.deqf(k));   // |coefficient * deq| < 2^24: exact
     fidct8(c);   // dct_inverse_transform_columns
     f_cols_to_rows(c, mb, i, m & 3);
     fidct8(c);   // dct_inverse_transform_rows
 #pragma unroll
     for (int k = 0; k < 8; k++) c[k] = PIXEL ? iframe_pixel_f(c[k]) : f2floor(c[k] * f2s(1.0f / 256.0f));     // v >> 8: |v| < 2^24, exact
+}
+template <bool PIXEL>
+__device__ __forceinline__ void inverse_half_f(f2 (&c)[8], int *xw, int m, int i, const LaneQ &lq)
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = c[k] * f2s(lq.deqf(k));   // |coefficient * deq| < 2^24: exact
+    inverse_transform_half_f<PIXEL>(c, xw, m, i);
 }
 // 16 reconstructed pixels (floats, integer-valued) -> saturated bytes: v_cvt_pk_u8_f32 clamps to 0..255 and places the byte
 __device__ __forceinline__ uint4 pack_row_f(const f2 (&px)[8])
@@ -792,6 +807,40 @@ __device__ __forceinline__ void unpack_row_f(const uint4 &row, f2 (&px)[8])
         px[k] = f2{(float)byte_of(row.x, k), (float)byte_of(row.z, k)};
         px[k + 4] = f2{(float)byte_of(row.y, k), (float)byte_of(row.w, k)};
     }
+}
+
+// ------------------------------------------------------------------ the decoders' float inverse, behind a guard
+// A decoder cannot argue from its tables as the encoders do: any i16 coefficient times any table entry may arrive, and the reference
+// then wraps in i32.  So the decode kernels dequantise in integers as ever (v = wmul24(c, deq), wrapped where the reference wraps),
+// look at the values v of a pass -- the lane's sixteen, over the whole wavefront -- and take the float transform only if every one
+// satisfies |v| <= kDecFloatGuard; otherwise the whole wavefront runs the integer transform for that pass.  The float path starts
+// from the integer v (v_cvt_f32_i32, exact below 2^24), never from float(c) * float(deq).
+// kDecFloatGuard: with I the matrix of |coefficients| of the 1-D inverse (tests/test_float_exact.py: _abs_matrix(idct)), R its largest
+// row sum = 121/16 (rows 0, 3, 4, 7: 1 + 1.1875 + 1.25 + 1.4375 + 1 + 0.9375 + 0.5 + 0.25) and s = 16 the slack for the truncating
+// divisions (at most 5 truncated quotients reach an output, each off by less than 1), a pass maps inputs bounded by M to outputs
+// bounded by R M + s; every intermediate of fidct8 is a sum of fewer of the same terms and obeys the same bound.  Columns then rows:
+// |x| <= R (R T + s) + s, and that must stay below 2^23 -- one bit under the 2^24 up to which f32 holds every integer, as in the
+// encoders' proof.  R^2 T + R s + s < 2^23  <=>  T < (2^23 - 137) * 256 / 14641 = 146673.6...  (tests/test_dec_float_bound.py
+// recomputes this from the oracle's idct and checks the float evaluation against it bit for bit at and below the bound.)
+constexpr int kDecFloatGuard = 146673;
+static_assert(14641LL * kDecFloatGuard + 256LL * (121 + 16) < 256LL * (1 << 23) && 14641LL * (kDecFloatGuard + 1) + 256LL * (121 + 16) >= 256LL * (1 << 23),
+              "kDecFloatGuard is the largest T with R (R T + s) + s < 2^23, R = 121/16, s = 16");
+// `live`: the lane's values count (lanes of skipped macroblocks pass false: their values are masked out of the result).  One
+// v_max3_i32 and one v_min3_i32 chain per lane, one vote per wavefront.
+__device__ __forceinline__ bool dec_float_guard(const int (&v)[2][8], bool live)
+{
+    int hi = v[0][0], lo = v[0][0];
+#pragma unroll
+    for (int k = 1; k < 16; k++) {
+        hi = max(hi, v[k >> 3][k & 7]);
+        lo = min(lo, v[k >> 3][k & 7]);
+    }
+    return !__any(live && (hi > kDecFloatGuard || lo < -kDecFloatGuard));
+}
+__device__ __forceinline__ void dequantised_to_f(const int (&v)[2][8], f2 (&c)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = f2{(float)v[0][k], (float)v[1][k]};
 }
 
 // ================================================================== I-frame encode (+ closed-loop reconstruction)
@@ -1269,6 +1318,13 @@ __device__ __forceinline__ void opaque_row(uint4 &r)   // the compiler must not 
 #else
     (void)r;
 #endif
+}
+__device__ __forceinline__ int opaque_int(int x)   // the same for one value
+{
+#ifndef PFV_HIPEMU
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
 }
 template <bool FLT, bool REUNPACK = false, class Store>
 __device__ __forceinline__ uint4 penc_half(const uint4 &srow, const uint4 &prow, int *xw, int m, int i, const LaneQ &lq, float qmagic, bool want_recon,
@@ -1905,13 +1961,39 @@ __global__ __launch_bounds__(kThreads16) void k_enc_pframe16(FrameGeom g, const 
     }
 }
 
+// Wavefronts per SIMD the float forms of the decode kernels are compiled for: what the integer forms reach on their own (66 and 79 VGPRs).
+// Left alone, the float forms take 96 and 110 registers (5 and 4 wavefronts): the scheduler lets the second pass's coefficients, both patch
+// rows and the float rows overlap.  The integer forms carry no attribute and compile as before.
+constexpr int kDecIWaves = 7, kDecPWaves = 6;
+// What it took to fit them (profiles/dec_f32_inverse.md), all in the float forms only: the second pass works from lane indices the compiler
+// cannot equate with the first pass's (opaque_int), so that no LDS address or table entry of pass 0 is kept for pass 1; the integer road,
+// which hardly ever runs, forms its own LDS addresses the same way; the patch row stays packed across the transform; and the lane's
+// store address is the strip's wave-uniform base plus a 32-bit lane offset formed at the store (dec_row_ptr) instead of a 64-bit
+// pointer per lane that lives through both passes.
+__device__ __forceinline__ uint8_t *dec_row_ptr(uint8_t *strip, int lane_offset) { return strip + (unsigned)opaque_int(lane_offset); }
+// a wave-uniform pointer, said so: without it the compiler sinks the geometry reads behind it into divergent branches and carries the
+// merged value in vector registers
+__device__ __forceinline__ uint8_t *wave_uniform(uint8_t *p)
+{
+    const uintptr_t a = (uintptr_t)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    return (uint8_t *)(((uintptr_t)hi << 32) | lo);
+}
+#ifdef PFV_HIPEMU
+#define PFV_DEC_WAVES_PER_EU(flt, n)
+#else
+#define PFV_DEC_WAVES_PER_EU(flt, n) __attribute__((amdgpu_waves_per_eu((flt) ? (n) : 1, (flt) ? (n) : 8)))
+#endif
+
 // ================================================================== I-frame decode
 // reference: VideoPlane::decode_plane / decode_plane_into (src/common.rs:423-446, 477-496)
 // frames_out != nullptr: also write the cropped, tightly packed retframe (n_streams frames).
-template <int LPM = 8, bool LISTS = false>
-__global__ __launch_bounds__(kThreads) void k_dec_iframe(FrameGeom g, const int16_t *__restrict__ coef, CoefLists cl,
+// FLT: the inverse transform in f32 for every pass whose dequantised values pass dec_float_guard, in i32 otherwise (false: always i32).
+// int_path_waves (nullable, FLT only): += 1 per wavefront that ran a pass in i32 (pfv_dec_session_enable_path_stats).
+template <int LPM = 8, bool LISTS = false, bool FLT = false>
+__global__ __launch_bounds__(kThreads) PFV_DEC_WAVES_PER_EU(FLT, kDecIWaves) void k_dec_iframe(FrameGeom g, const int16_t *__restrict__ coef, CoefLists cl,
                                                           uint8_t *__restrict__ out, const QTab *__restrict__ qtabs,
-                                                          uint8_t *__restrict__ frames_out)
+                                                          uint8_t *__restrict__ frames_out, int *__restrict__ int_path_waves)
 {
     __shared__ __attribute__((aligned(16))) int xchg[kStripsPerWG][kXchgDwords];
     __shared__ __attribute__((aligned(16))) int qtab_lds[kStripsPerWG][kQTabDwords];
@@ -1924,6 +2006,8 @@ __global__ __launch_bounds__(kThreads) void k_dec_iframe(FrameGeom g, const int1
     const StripPos sp = locate_strip(g, gstrip);
     if (half_strip * 4 >= sp.n_mb) return;
     const PlaneGeom &p = g.p[sp.plane];
+    const int pw_u = FLT ? __builtin_amdgcn_readfirstlane(p.pw) : 0;   // FLT: see wave_uniform
+    const auto pw = [&]() { return FLT ? pw_u : p.pw; };
     const int slot = lane >> 3, i = lane & 7;
     const int m = LPM == 8 ? slot : half_strip * 4 + (slot >> 1);
     int *xw = xchg[wave];
@@ -1944,28 +2028,54 @@ __global__ __launch_bounds__(kThreads) void k_dec_iframe(FrameGeom g, const int1
     }
     fill_qtable<false>(qtab_lds[wave], qtabs + p.qsel, lane);
     wave_lds_sync();
-    const LaneQ lq{qtab_lds[wave], i};
-    uint8_t *dst = out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(sp.y0 + i) * p.pw + sp.x0 + m * 16;
+    uint8_t *dst = FLT ? nullptr : out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(sp.y0 + i) * pw() + sp.x0 + m * 16;
+    uint8_t *out_strip = FLT ? wave_uniform(out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)sp.y0 * pw() + sp.x0) : nullptr;   // dec_row_ptr
+    bool int_pass = false;   // wave-uniform
 #pragma unroll
     for (int pass = 0; pass < kPasses; pass++) {
         const int h = LPM == 8 ? pass : (slot & 1);
-        if (LISTS) stage_list_half<LPM>(xw, span, lane, sp.mb_first + half_strip * 4, pass);
-        else stage_coef_half(xw, cbuf[pass], lane);
+        int ip = i, slotp = slot, lanep = lane;
+        if (FLT && pass) {   // see kDecIWaves
+            ip = opaque_int(i); slotp = opaque_int(slot); lanep = opaque_int(lane);
+            if (LISTS) { span.e0 = (uint32_t)opaque_int((int)span.e0); span.e1 = (uint32_t)opaque_int((int)span.e1); }
+        }
+        if (LISTS) stage_list_half<LPM>(xw, span, lanep, sp.mb_first + half_strip * 4, pass);
+        else stage_coef_half(xw, cbuf[pass], lanep);
         wave_lds_sync();
         int v[2][8];
-        gather_half(v, xw, slot, lq);
-        inverse_half(v, xw, slot, i, lq);
+        const LaneQ lq{qtab_lds[wave], ip};
+        gather_half(v, xw, slotp, lq);
+        dequant_half(v, lq);
+        uint4 o;
+        if (FLT && dec_float_guard(v, true)) {   // absent macroblocks hold zeros
+            f2 c[8];
+            dequantised_to_f(v, c);
+            inverse_transform_half_f<true>(c, xw, slotp, ip);   // (x >> 8) + 128, clamped by the pack's rounding + saturation (iframe_pixel_f)
+            o = pack_row_f(c);
+        } else {
+            int_pass = FLT;
+            if (FLT) inverse_transform_half(v, xw, opaque_int(slot), opaque_int(i));   // the cold road forms its LDS addresses itself
+            else inverse_transform_half(v, xw, slot, i);
 #pragma unroll
-        for (int s = 0; s < 2; s++)
+            for (int s = 0; s < 2; s++)
 #pragma unroll
-            for (int k = 0; k < 8; k++) v[s][k] = min(max(v[s][k] + 128, 0), 255);   // src/common.rs:321
-        if (m < sp.n_mb) {
-            const uint4 o = pack_row(v);
-            *reinterpret_cast<uint4 *>(dst + (long)(8 * h) * p.pw) = o;
+                for (int k = 0; k < 8; k++) v[s][k] = min(max(v[s][k] + 128, 0), 255);   // src/common.rs:321
+            o = pack_row(v);
+        }
+        int is = i, hs = h, ms = m;
+        if (FLT) {   // the row's place from the lane index again: one register across the transform instead of three
+            const int l = opaque_int(lane);
+            is = l & 7;
+            hs = LPM == 8 ? pass : ((l >> 3) & 1);
+            ms = LPM == 8 ? l >> 3 : half_strip * 4 + (l >> 4);
+        }
+        if (ms < sp.n_mb) {
+            *reinterpret_cast<uint4 *>(FLT ? dec_row_ptr(out_strip, (is + 8 * hs) * pw() + ms * 16) : dst + (long)(8 * h) * pw()) = o;
             if (frames_out)
-                store_cropped16(frames_out + (long)sp.stream * g.src_frame_bytes + p.src_off, p, sp.x0 + m * 16, sp.y0 + i + 8 * h, o);
+                store_cropped16(frames_out + (long)sp.stream * g.src_frame_bytes + p.src_off, p, sp.x0 + ms * 16, sp.y0 + is + 8 * hs, o);
         }
     }
+    if (FLT && int_pass && int_path_waves && lane == 0) atomicAdd(int_path_waves, 1);
 }
 
 // ================================================================== P-frame decode
@@ -1974,12 +2084,13 @@ __global__ __launch_bounds__(kThreads) void k_dec_iframe(FrameGeom g, const int1
 // reference reads every patch from the old plane before it writes anything (:498-521).
 // err_flag[stream] is set when a motion vector leaves the plane (:258-259 debug_assert); the
 // vector is then treated as (0,0) so that no out-of-bounds access happens.
-template <int LPM = 8, bool LISTS = false>
-__global__ __launch_bounds__(kThreads) void k_dec_pframe(FrameGeom g, const int8_t *__restrict__ mv,
+// FLT, int_path_waves: as for k_dec_iframe.
+template <int LPM = 8, bool LISTS = false, bool FLT = false>
+__global__ __launch_bounds__(kThreads) PFV_DEC_WAVES_PER_EU(FLT, kDecPWaves) void k_dec_pframe(FrameGeom g, const int8_t *__restrict__ mv,
                                                           const uint8_t *__restrict__ has, const int16_t *__restrict__ coef, CoefLists cl,
                                                           const uint8_t *__restrict__ ref, uint8_t *__restrict__ out,
                                                           const QTab *__restrict__ qtabs, int *__restrict__ err_flag,
-                                                          uint8_t *__restrict__ frames_out)
+                                                          uint8_t *__restrict__ frames_out, int *__restrict__ int_path_waves)
 {
     __shared__ __attribute__((aligned(16))) int xchg[kStripsPerWG][kXchgDwords];
     __shared__ __attribute__((aligned(16))) int qtab_lds[kStripsPerWG][kQTabDwords];
@@ -1992,6 +2103,8 @@ __global__ __launch_bounds__(kThreads) void k_dec_pframe(FrameGeom g, const int8
     const StripPos sp = locate_strip(g, gstrip);
     if (half_strip * 4 >= sp.n_mb) return;
     const PlaneGeom &p = g.p[sp.plane];
+    const int pw_u = FLT ? __builtin_amdgcn_readfirstlane(p.pw) : 0;   // FLT: see wave_uniform
+    const auto pw = [&]() { return FLT ? pw_u : p.pw; };
     const int slot = lane >> 3, i = lane & 7;
     const int m = LPM == 8 ? slot : half_strip * 4 + (slot >> 1);
     int *xw = xchg[wave];
@@ -2014,7 +2127,7 @@ __global__ __launch_bounds__(kThreads) void k_dec_pframe(FrameGeom g, const int8
     const int mbx = sp.x0 + m * 16, mby = sp.y0;
     if (mb_valid) {
         int sx = mbx + mx, sy = mby + my;
-        if (sx < 0 || sx > p.pw - 16 || sy < 0 || sy > p.ph - 16) {
+        if (sx < 0 || sx > pw() - 16 || sy < 0 || sy > p.ph - 16) {
             if (i == 0) atomicOr(err_flag + sp.stream, 1);   // one flag per stream of the launch
             mx = 0; my = 0;
         }
@@ -2038,44 +2151,73 @@ __global__ __launch_bounds__(kThreads) void k_dec_pframe(FrameGeom g, const int8
 #pragma unroll
     for (int pass = 0; pass < kPasses; pass++) patch[pass] = make_uint4(0, 0, 0, 0);
     if (mb_valid) {   // the lane's rows of the motion-compensated patch (get_block, :327-339)
-        const uint8_t *rp = ref + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(mby + my + i) * p.pw + (mbx + mx);
+        const uint8_t *rp = ref + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(mby + my + i) * pw() + (mbx + mx);
 #pragma unroll
-        for (int pass = 0; pass < kPasses; pass++) patch[pass] = load_unaligned16(rp + 8 * (long)(LPM == 8 ? pass : (slot & 1)) * p.pw);
+        for (int pass = 0; pass < kPasses; pass++) patch[pass] = load_unaligned16(rp + 8 * (long)(LPM == 8 ? pass : (slot & 1)) * pw());
     }
-    uint8_t *dst = out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(sp.y0 + i) * p.pw + mbx;
+    uint8_t *dst = FLT ? nullptr : out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)(sp.y0 + i) * pw() + mbx;
+    uint8_t *out_strip = FLT ? wave_uniform(out + (long)sp.stream * g.pad_frame_bytes + p.pad_off + (long)sp.y0 * pw() + sp.x0) : nullptr;   // dec_row_ptr
     uint8_t *crop = frames_out ? frames_out + (long)sp.stream * g.src_frame_bytes + p.src_off : nullptr;
 
     if (any_coded) {
         wave_lds_sync();
-        const LaneQ lq{qtab_lds[wave], i};
+        bool int_pass = false;   // wave-uniform
 #pragma unroll
         for (int pass = 0; pass < kPasses; pass++) {
             const int h = LPM == 8 ? pass : (slot & 1);
-            if (LISTS) stage_list_half<LPM>(xw, span, lane, sp.mb_first + half_strip * 4, pass);
-            else stage_coef_half(xw, cbuf[pass], lane);
+            int ip = i, slotp = slot, lanep = lane;
+            if (FLT && pass) {   // see kDecIWaves
+                ip = opaque_int(i); slotp = opaque_int(slot); lanep = opaque_int(lane);
+                if (LISTS) { span.e0 = (uint32_t)opaque_int((int)span.e0); span.e1 = (uint32_t)opaque_int((int)span.e1); }
+            }
+            if (LISTS) stage_list_half<LPM>(xw, span, lanep, sp.mb_first + half_strip * 4, pass);
+            else stage_coef_half(xw, cbuf[pass], lanep);
             wave_lds_sync();
-            int v[2][8], pp[2][8];
-            const int codedmask = coded ? -1 : 0;
-            gather_half(v, xw, slot, lq);
-            inverse_half(v, xw, slot, i, lq);
-            unpack_row(patch[pass], pp);
+            int v[2][8];
+            const LaneQ lq{qtab_lds[wave], ip};
+            gather_half(v, xw, slotp, lq);
+            dequant_half(v, lq);
+            uint4 o;
+            if (FLT && dec_float_guard(v, coded)) {   // a skipped macroblock's coefficients are not read by the reference: whatever they are
+                f2 c[8], pp[8];
+                dequantised_to_f(v, c);
+                inverse_transform_half_f<false>(c, xw, slotp, ip);
+                uint4 prow = patch[pass];
+                opaque_row(prow);   // the patch row stays packed across the transform (as in penc_half, REUNPACK)
+                unpack_row_f(prow, pp);
+                const f2 twice = f2s((float)opaque_int(coded ? 2 : 0));   // 0 for skipped blocks: copy (every value of the float path is finite)
 #pragma unroll
-            for (int s = 0; s < 2; s++)
+                for (int k = 0; k < 8; k++) {   // apply_residuals (:98-104): prev + 2 * min(t, 127), saturated by the pack
+                    const f2 t = f2{__builtin_fminf(c[k][0], 127.0f), __builtin_fminf(c[k][1], 127.0f)};
+                    pp[k] = pp[k] + t * twice;
+                }
+                o = pack_row_f(pp);
+            } else {
+                int_pass = FLT;
+                int pp[2][8];
+                const int codedmask = coded ? -1 : 0;
+                if (FLT) inverse_transform_half(v, xw, opaque_int(slot), opaque_int(i));   // the cold road forms its LDS addresses itself
+                else inverse_transform_half(v, xw, slot, i);
+                unpack_row(patch[pass], pp);
 #pragma unroll
-                for (int k = 0; k < 8; k++)   // apply_residuals (:98-104); masked to 0 for skipped blocks: copy
-                    pp[s][k] = min(max(pp[s][k] + 2 * (v[s][k] & codedmask), 0), 255);
+                for (int s = 0; s < 2; s++)
+#pragma unroll
+                    for (int k = 0; k < 8; k++)   // apply_residuals (:98-104); masked to 0 for skipped blocks: copy
+                        pp[s][k] = min(max(pp[s][k] + 2 * (v[s][k] & codedmask), 0), 255);
+                o = pack_row(pp);
+            }
             if (mb_valid) {
-                const uint4 o = pack_row(pp);
-                *reinterpret_cast<uint4 *>(dst + (long)(8 * h) * p.pw) = o;
-                if (crop) store_cropped16(crop, p, mbx, sp.y0 + i + 8 * h, o);
+                *reinterpret_cast<uint4 *>(FLT ? dec_row_ptr(out_strip, (i + 8 * h) * pw() + m * 16) : dst + (long)(8 * h) * pw()) = o;
+                if (crop) store_cropped16(crop, p, FLT ? sp.x0 + opaque_int(m) * 16 : mbx, sp.y0 + i + 8 * h, o);
             }
         }
+        if (FLT && int_pass && int_path_waves && lane == 0) atomicAdd(int_path_waves, 1);
     } else if (mb_valid) {
 #pragma unroll
         for (int pass = 0; pass < kPasses; pass++) {
             const int h = LPM == 8 ? pass : (slot & 1);
-            *reinterpret_cast<uint4 *>(dst + (long)(8 * h) * p.pw) = patch[pass];
-            if (crop) store_cropped16(crop, p, mbx, sp.y0 + i + 8 * h, patch[pass]);
+            *reinterpret_cast<uint4 *>(FLT ? dec_row_ptr(out_strip, (i + 8 * h) * pw() + m * 16) : dst + (long)(8 * h) * pw()) = patch[pass];
+            if (crop) store_cropped16(crop, p, FLT ? sp.x0 + opaque_int(m) * 16 : mbx, sp.y0 + i + 8 * h, patch[pass]);
         }
     }
 }

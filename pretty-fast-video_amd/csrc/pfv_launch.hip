@@ -221,28 +221,54 @@ struct DecCoefs {
         return c;
     }
 };
-static void launch_dec_iframe(pfv_ctx *ctx, bool small, const FrameGeom &g, const DecCoefs &c, uint8_t *out, const QTab *qt, uint8_t *frames_out)
+// flt: the guarded float inverse (PFV_DEC_TRANSFORM_AUTO), false: the i32 kernels; int_path_waves: nullable counter, see k_dec_iframe
+template <int LPM, bool LISTS>
+static void launch_dec_iframe_as(pfv_ctx *ctx, bool flt, dim3 grid, const FrameGeom &g, const DecCoefs &c, uint8_t *out, const QTab *qt, uint8_t *frames_out,
+                                 int *int_path_waves)
 {
-    const dim3 grid(small ? half_strip_blocks(g) : strip_blocks(g)), block(kThreads);
+    if (flt) hipLaunchKernelGGL((k_dec_iframe<LPM, LISTS, true>), grid, dim3(kThreads), 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out, int_path_waves);
+    else hipLaunchKernelGGL((k_dec_iframe<LPM, LISTS, false>), grid, dim3(kThreads), 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out, (int *)nullptr);
+}
+static void launch_dec_iframe(pfv_ctx *ctx, bool flt, bool small, const FrameGeom &g, const DecCoefs &c, uint8_t *out, const QTab *qt, uint8_t *frames_out,
+                              int *int_path_waves = nullptr)
+{
+    const dim3 grid(small ? half_strip_blocks(g) : strip_blocks(g));
     if (c.is_lists()) {
-        if (small) hipLaunchKernelGGL((k_dec_iframe<16, true>), grid, block, 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out);
-        else hipLaunchKernelGGL((k_dec_iframe<8, true>), grid, block, 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out);
+        if (small) launch_dec_iframe_as<16, true>(ctx, flt, grid, g, c, out, qt, frames_out, int_path_waves);
+        else launch_dec_iframe_as<8, true>(ctx, flt, grid, g, c, out, qt, frames_out, int_path_waves);
     } else {
-        if (small) hipLaunchKernelGGL((k_dec_iframe<16, false>), grid, block, 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out);
-        else hipLaunchKernelGGL((k_dec_iframe<8, false>), grid, block, 0, ctx->stream, g, c.dense, c.lists, out, qt, frames_out);
+        if (small) launch_dec_iframe_as<16, false>(ctx, flt, grid, g, c, out, qt, frames_out, int_path_waves);
+        else launch_dec_iframe_as<8, false>(ctx, flt, grid, g, c, out, qt, frames_out, int_path_waves);
     }
 }
-static void launch_dec_pframe(pfv_ctx *ctx, bool small, const FrameGeom &g, const int8_t *mv, const uint8_t *has, const DecCoefs &c, const uint8_t *ref,
-                              uint8_t *out, const QTab *qt, int *flag, uint8_t *frames_out)
+template <int LPM, bool LISTS>
+static void launch_dec_pframe_as(pfv_ctx *ctx, bool flt, dim3 grid, const FrameGeom &g, const int8_t *mv, const uint8_t *has, const DecCoefs &c, const uint8_t *ref,
+                                 uint8_t *out, const QTab *qt, int *flag, uint8_t *frames_out, int *int_path_waves)
 {
-    const dim3 grid(small ? half_strip_blocks(g) : strip_blocks(g)), block(kThreads);
+    if (flt) hipLaunchKernelGGL((k_dec_pframe<LPM, LISTS, true>), grid, dim3(kThreads), 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out, int_path_waves);
+    else hipLaunchKernelGGL((k_dec_pframe<LPM, LISTS, false>), grid, dim3(kThreads), 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out, (int *)nullptr);
+}
+static void launch_dec_pframe(pfv_ctx *ctx, bool flt, bool small, const FrameGeom &g, const int8_t *mv, const uint8_t *has, const DecCoefs &c, const uint8_t *ref,
+                              uint8_t *out, const QTab *qt, int *flag, uint8_t *frames_out, int *int_path_waves = nullptr)
+{
+    const dim3 grid(small ? half_strip_blocks(g) : strip_blocks(g));
     if (c.is_lists()) {
-        if (small) hipLaunchKernelGGL((k_dec_pframe<16, true>), grid, block, 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out);
-        else hipLaunchKernelGGL((k_dec_pframe<8, true>), grid, block, 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out);
+        if (small) launch_dec_pframe_as<16, true>(ctx, flt, grid, g, mv, has, c, ref, out, qt, flag, frames_out, int_path_waves);
+        else launch_dec_pframe_as<8, true>(ctx, flt, grid, g, mv, has, c, ref, out, qt, flag, frames_out, int_path_waves);
     } else {
-        if (small) hipLaunchKernelGGL((k_dec_pframe<16, false>), grid, block, 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out);
-        else hipLaunchKernelGGL((k_dec_pframe<8, false>), grid, block, 0, ctx->stream, g, mv, has, c.dense, c.lists, ref, out, qt, flag, frames_out);
+        if (small) launch_dec_pframe_as<16, false>(ctx, flt, grid, g, mv, has, c, ref, out, qt, flag, frames_out, int_path_waves);
+        else launch_dec_pframe_as<8, false>(ctx, flt, grid, g, mv, has, c, ref, out, qt, flag, frames_out, int_path_waves);
     }
+}
+// wavefronts of a decode launch that own a macroblock (the unit of pfv_dec_session_path_stats)
+static long dec_launch_waves(bool small, const FrameGeom &g)
+{
+    long per_frame = 0;
+    for (int i = 0; i < g.n_planes; i++) {
+        const PlaneGeom &p = g.p[i];
+        per_frame += (long)p.bh * (small ? (p.bw + 3) / 4 : p.strips_x);
+    }
+    return per_frame * g.n_streams;
 }
 
 static int launch_check(pfv_ctx *ctx, const char *what)

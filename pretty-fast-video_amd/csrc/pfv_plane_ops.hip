@@ -74,7 +74,7 @@ PFV_API int pfv_decode_plane_into(pfv_ctx *ctx, const int16_t *coef, int bw, int
     if ((rc = ensure_scratch(ctx, 1, coef_bytes, &d_coef))) return rc;
     if ((rc = ensure_scratch(ctx, 5, pad_bytes, &d_out))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_coef, coef, coef_bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch_dec_iframe(ctx, use_small_grid(ctx->opt_lane_mapping, g), g, (const int16_t *)d_coef, (uint8_t *)d_out, ctx->qtab_dev, nullptr);
+    launch_dec_iframe(ctx, ctx->opt_dec_transform != PFV_DEC_TRANSFORM_INT, use_small_grid(ctx->opt_lane_mapping, g), g, (const int16_t *)d_coef, (uint8_t *)d_out, ctx->qtab_dev, nullptr);
     if ((rc = launch_check(ctx, "k_dec_iframe"))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(target, d_out, pad_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -104,7 +104,7 @@ PFV_API int pfv_decode_plane_delta(pfv_ctx *ctx, const int8_t *mv, const uint8_t
     HIP_TRY(ctx, hipMemcpyAsync(d_mv, mv, n * 2, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_has, has_coef, n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->flag_dev, 0, sizeof(int), ctx->stream));
-    launch_dec_pframe(ctx, use_small_grid(ctx->opt_lane_mapping, g), g, (const int8_t *)d_mv, (const uint8_t *)d_has, (const int16_t *)d_coef, (const uint8_t *)d_ref,
+    launch_dec_pframe(ctx, ctx->opt_dec_transform != PFV_DEC_TRANSFORM_INT, use_small_grid(ctx->opt_lane_mapping, g), g, (const int8_t *)d_mv, (const uint8_t *)d_has, (const int16_t *)d_coef, (const uint8_t *)d_ref,
                       (uint8_t *)d_out, ctx->qtab_dev, ctx->flag_dev, nullptr);
     if ((rc = launch_check(ctx, "k_dec_pframe"))) return rc;
     int flag = 0;

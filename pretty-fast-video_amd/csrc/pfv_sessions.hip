@@ -162,6 +162,9 @@ struct pfv_dec_session {
     QTab *qtab_dev = nullptr;
     uint8_t *fb[2] = {nullptr, nullptr};     // ping-pong framebuffer
     int lane_mapping = PFV_LANES_AUTO;       // PFV_OPT_LANE_MAPPING at creation
+    bool flt = true;                         // PFV_OPT_DEC_TRANSFORM at creation: the guarded float inverse (false: the i32 kernels)
+    int *path_dev = nullptr;                 // pfv_dec_session_enable_path_stats: wavefronts that ran a pass in i32 (null: not counted)
+    long path_total = 0;                     // wavefronts launched since then
     int cur = 0;
     int *flag_dev = nullptr;                 // [n_streams]: a p-frame decode met a motion vector that leaves the plane
     std::vector<int> flags_host;
@@ -788,6 +791,7 @@ PFV_API int pfv_dec_session_create(pfv_ctx *ctx, int width, int height, const in
     s->ctx = ctx; s->width = width; s->height = height; s->n_streams = n_streams; s->n_qtables = n_qtables;
     s->win_count = n_streams;
     s->lane_mapping = ctx->opt_lane_mapping;
+    s->flt = ctx->opt_dec_transform != PFV_DEC_TRANSFORM_INT;
     s->geom = frame_geom(width, height, n_streams);
     s->db_table.resize((size_t)n_dev);
     for (int i = 0; i < n_dev; i++) s->db_table[(size_t)i] = (uint8_t)pfv_deblock_strength(qtables + (size_t)i * 64);
@@ -816,7 +820,7 @@ PFV_API void pfv_dec_session_destroy(pfv_dec_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map, s->ssim_map, s->db_scratch, s->st_rgb};
+    void *bufs[] = {s->qtab_dev, s->fb[0], s->fb[1], s->flag_dev, s->st_coef, s->st_mv, s->st_has, s->st_frames, s->st_idx, s->st_val, s->q_map, s->ssim_map, s->db_scratch, s->st_rgb, s->path_dev};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -843,6 +847,36 @@ PFV_API int pfv_dec_session_set_window(pfv_dec_session *s, int first, int count)
     if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
     if (first < 0 || count <= 0 || first > s->n_streams - count) return fail(s->ctx, PFV_ERR_BAD_ARG, "pfv_dec_session_set_window: window outside [0, n_streams)");
     s->win_first = first; s->win_count = count;
+    return PFV_OK;
+}
+// Which road the inverse transform took (PFV_OPT_DEC_TRANSFORM, pfv_hip_ext.h).  on: start (or restart) counting from zero; off: stop.
+PFV_API int pfv_dec_session_enable_path_stats(pfv_dec_session *s, int on)
+{
+    if (!s) return fail(nullptr, PFV_ERR_BAD_ARG, "null session");
+    pfv_ctx *ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!on) {
+        if (s->path_dev) HIP_TRY(ctx, hipFree(s->path_dev));
+        s->path_dev = nullptr;
+        return PFV_OK;
+    }
+    if (!s->path_dev) HIP_TRY(ctx, hipMalloc((void **)&s->path_dev, sizeof(int)));
+    HIP_TRY(ctx, hipMemset(s->path_dev, 0, sizeof(int)));
+    s->path_total = 0;
+    return PFV_OK;
+}
+PFV_API int pfv_dec_session_path_stats(pfv_dec_session *s, int64_t *int_waves, int64_t *total_waves)
+{
+    if (!s || !int_waves || !total_waves) return fail(s ? s->ctx : nullptr, PFV_ERR_BAD_ARG, "pfv_dec_session_path_stats: bad argument");
+    pfv_ctx *ctx = s->ctx;
+    if (!s->path_dev) return fail(ctx, PFV_ERR_STATE, "pfv_dec_session_path_stats: not enabled (pfv_dec_session_enable_path_stats)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int n = 0;
+    HIP_TRY(ctx, hipMemcpy(&n, s->path_dev, sizeof(int), hipMemcpyDeviceToHost));
+    *int_waves = n;
+    *total_waves = s->path_total;
     return PFV_OK;
 }
 static bool dec_full_window(const pfv_dec_session *s) { return s->win_first == 0 && s->win_count == s->n_streams && s->out_stride == 0; }
@@ -893,12 +927,14 @@ static int dec_launch(pfv_dec_session *s, bool pframe, int first, int count, con
     g = dec_out_geom(s, g, s->frames_out);
     g.n_streams = count;
     const int nxt = s->cur ^ 1;
+    const bool small = use_small_grid(s->lane_mapping, g);
+    if (s->path_dev) s->path_total += dec_launch_waves(small, g);
     if (pframe) {
-        launch_dec_pframe(ctx, use_small_grid(s->lane_mapping, g), g, mv_dev + mb0 * 2, has_dev + mb0, coefs.shifted((size_t)first, (size_t)s->geom.mbs_per_frame),
-                          s->fb[s->cur] + pad0, s->fb[nxt] + pad0, s->qtab_dev, s->flag_dev + first, crop);
+        launch_dec_pframe(ctx, s->flt, small, g, mv_dev + mb0 * 2, has_dev + mb0, coefs.shifted((size_t)first, (size_t)s->geom.mbs_per_frame),
+                          s->fb[s->cur] + pad0, s->fb[nxt] + pad0, s->qtab_dev, s->flag_dev + first, crop, s->path_dev);
         rc = launch_check(ctx, "k_dec_pframe");
     } else {
-        launch_dec_iframe(ctx, use_small_grid(s->lane_mapping, g), g, coefs.shifted((size_t)first, (size_t)s->geom.mbs_per_frame), s->fb[nxt] + pad0, s->qtab_dev, crop);
+        launch_dec_iframe(ctx, s->flt, small, g, coefs.shifted((size_t)first, (size_t)s->geom.mbs_per_frame), s->fb[nxt] + pad0, s->qtab_dev, crop, s->path_dev);
         rc = launch_check(ctx, "k_dec_iframe");
     }
     return rc;

@@ -467,6 +467,17 @@ class DecoderSession(_Geometry):
     def check(self):
         self.ctx.check(self.ctx._lib.pfv_dec_check(self.handle))
 
+    def enable_path_stats(self, on: bool = True):
+        """count the wavefronts whose inverse transform ran in i32 because their values failed the float guard, from zero
+        (pfv_dec_session_enable_path_stats; PFV_OPT_DEC_TRANSFORM)"""
+        self.ctx.check(self.ctx._lib.pfv_dec_session_enable_path_stats(self.handle, 1 if on else 0))
+
+    def path_stats(self):
+        """(integer-path wavefronts, wavefronts launched) since enable_path_stats (pfv_dec_session_path_stats)"""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.check(self.ctx._lib.pfv_dec_session_path_stats(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
     def get_frame(self) -> np.ndarray:
         """retframe of every stream (src/dec.rs:195-197): uint8 [n_streams, frame_bytes]."""
         out = np.empty((self.n_streams, self.frame_bytes), dtype=np.uint8)
